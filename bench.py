@@ -15,7 +15,15 @@ and Adam state are replicated, one RCCL sum-all-reduce of the [23*N] gradient bu
 Prints ONE JSON line (rank 0) with the driver's contract fields plus
   roofline     -- dominant kernel: algorithmic bytes per launch / mean launch time, the launch
                   time measured with HIP events on the launch stream inside the timed region
-  cpu_baseline -- the C oracle (oracle/gs_oracle.c, a "port") timed on a bounded sample.
+  cpu_baseline -- (--full) the C oracle (oracle/gs_oracle.c, a "port") timed on a bounded sample.
+
+A plain run sets up, warms up, times the K steps and prints the line.  Everything else it can measure or check --
+PSNR before / after, the untimed continuation to 200 steps, the ground-truth-moments A/B, BASELINE configs[1],
+the scaling model, the CPU baselines, the alignment / matching / condensation benches and, for N > 1, the isolated
+exchange, the replica check and the exchange forms -- runs only with --full (the --no-* options then leave parts out).
+
+--dump-outputs DIR writes what the last timed step computed (the parameters, gradients and Adam moments of a fixed,
+seeded sample of the Gaussians, and the step's loss) as DIR/<name>.npy; the inputs depend on the arguments only.
 """
 import argparse
 import json
@@ -43,6 +51,12 @@ def parse():
     ap.add_argument("--views", type=int, default=8)
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement and check beyond the headline (see the module docstring); the "
+                         "--no-* and --train-only options below leave parts of it out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (float32, the sample "
+                         "indices float64; a fixed seeded sample of at most 2^17 Gaussians, < 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-drift", action="store_true",
                     help="skip the untimed continuation to 200 steps that shows how the step time drifts as training "
@@ -465,6 +479,34 @@ def replica_checksum(P):
     return tot
 
 
+DUMP_SEED = 20240611
+DUMP_MAX_GAUSSIANS = 1 << 17
+DUMP_BUDGET_BYTES = 60 << 20
+
+
+def dump_outputs(out_dir, ops, P, bufs, loss):
+    """What the last timed step handed back to its caller, as float32 .npy files: the parameters (updated in place),
+    the [23N] gradient buffer and the two Adam moment buffers (block layout of ops.split_grads) for a fixed, seeded sample
+    of the Gaussians (sample_index, in ascending order), and the step's loss.  Same arguments -> same sample."""
+    N = P["means"].shape[0]
+    per_gaussian = 4 * (sum(t[:1].numel() for t in P.values()) + 23 * len(bufs)) + 8
+    k = min(N, DUMP_MAX_GAUSSIANS, DUMP_BUDGET_BYTES // per_gaussian)
+    idx = np.sort(np.random.Generator(np.random.PCG64(DUMP_SEED)).choice(N, size=k, replace=False))
+    sel = torch.from_numpy(idx).to(P["means"].device)
+    arrays = {"sample_index": idx.astype(np.float64), "loss": loss.detach().float().reshape(-1).cpu().numpy()}
+    for name in sorted(P):
+        arrays[f"param_{name}"] = P[name].index_select(0, sel).float().cpu().numpy()
+    for prefix, buf in bufs.items():
+        for name, t in ops.split_grads(buf, N).items():
+            arrays[f"{prefix}_{name}"] = t.index_select(0, sel).float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 << 20, f"output dump of {total} bytes exceeds 64 MB"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    return total
+
+
 def matching_bench(device, with_cpu=True):
     """Path A: seeded nearest-neighbour query of fast_reciprocal_NNs (starster/reconstruct.py:97) at the
     reference's size: 3072 seeds against the 512x384 descriptors (D = 24) of the other image -- the only dense
@@ -563,7 +605,8 @@ def main():
     mode = args.multi_gpu
     total = args.warmup + args.steps
     DRIFT_TO = 200   # SURVEY 8(d) asks for >= 200 steady-state iterations; the driver fixes --steps 20
-    want_drift = world == 1 and not FREEZE and not args.no_drift and args.steps < DRIFT_TO and mode != "gaussian-sharded"
+    want_drift = (args.full and world == 1 and not FREEZE and not args.no_drift and args.steps < DRIFT_TO
+                  and mode != "gaussian-sharded")
     losses = torch.zeros(max(total, args.warmup + DRIFT_TO) if want_drift else total, device=device)
     stats = {}
     gtm_ms = None
@@ -576,6 +619,7 @@ def main():
         gt = make_gt_images(ctx, ops, g_np, w2c, Ks, W, H, device)
         P = {k: torch.tensor(np.ascontiguousarray(v[lo:hi]), device=device) for k, v in g_np.items()}
         trainer = sdist.ShardedTrainer(ctx, P, N, w2c_all, Ks_all, gt, W, H, rank, world)
+        dump_bufs = {}
 
         def step(it):
             return trainer.step(losses[it:it + 1])
@@ -592,6 +636,7 @@ def main():
         gt = make_gt_images(ctx, ops, g_np, w2c, Ks, W, H, device)
         grads = torch.empty(23 * N, device=device)
         m = torch.zeros_like(grads); v = torch.zeros_like(grads)
+        dump_bufs = {"grad": grads, "adam_m": m, "adam_v": v}
         # like gs.run_3dgs_optim: SSIM's two ground-truth moments conv(gt), conv(gt^2) are computed ONCE per training call
         # (the images do not change inside it, starster/gs.py:149-152) and registered with the ctx; the timed steps read
         # them.  The pre-pass is timed here and reported (config.gt_moments_once_per_call_ms).  ST3R_BENCH_GT_MOMENTS=0:
@@ -643,7 +688,7 @@ def main():
             rgb, _, _ = ops.render(ctx, P, w2c, Ks, ops.camera_positions(w2c), W, H)
             mse = ((rgb.clamp(0, 1) - gt) ** 2).reshape(rgb.shape[0], -1).mean(1)
             return float((-10.0 * torch.log10(mse)).mean())
-    psnr_before = psnr_local()
+    psnr_before = psnr_local() if args.full else None
 
     # Stage timing costs two HIP events per stage and step (~0.15 ms per step for all eleven): the warm-up steps time
     # every stage to find the dominant one; in the timed region ONE stage is timed per step (two events, live, on the
@@ -681,7 +726,10 @@ def main():
     win_ms = [marks[edges[k]].elapsed_time(marks[edges[k + 1]]) / (edges[k + 1] - edges[k]) for k in range(n_win)]
     stage = ops.stage_ms(ctx)
     ops.set_profiling(ctx, False)
-    psnr_after = psnr_local()
+    # what the last timed step computed, before anything below runs more steps on the same state
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ops, P, dump_bufs, losses[total - 1:total])
+    psnr_after = psnr_local() if args.full else None
     # The reference trains RAW scales: the Gaussians grow and the step gets slower with the step count.
     # Untimed continuation of the same run to 200 steps: the step time at steps 100-120 and 180-200 next to the timed one.
     drift = None
@@ -704,7 +752,7 @@ def main():
     # itself, like torchmetrics inside the reference's compute_loss) -- so that the line also carries the rate a reader gets
     # who counts the moments as per-iteration work
     gtm_delta_ms = None
-    if gtm_ms is not None and world == 1 and not FREEZE and mode != "gaussian-sharded":
+    if args.full and gtm_ms is not None and world == 1 and not FREEZE and mode != "gaussian-sharded":
         it_x = max(losses.numel() - 2, 1)   # (not the first / last index: those ask for statistics, i.e. the synchronous path)
         acc = {True: 0.0, False: 0.0}
         for blk in range(6):
@@ -726,7 +774,7 @@ def main():
         t_all = [torch.zeros(1, device=device, dtype=torch.float64) for _ in range(world)]
         dist.all_gather(t_all, torch.tensor([my_ms], device=device, dtype=torch.float64))
         per_rank_ms = [float(x.item()) for x in t_all]
-        if mode != "gaussian-sharded":
+        if args.full and mode != "gaussian-sharded":
             from starst3r_amd import _lib
             scratch = torch.zeros(23 * N, device=device)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -751,7 +799,7 @@ def main():
         ws, rk = ctypes.c_int(0), ctypes.c_int(0)
         _l.check(_l.lib().st3r_comm_world(ctx.handle, ctypes.byref(ws), ctypes.byref(rk)))
         n_ranks_seen = int(ws.value)
-        if dist is not None:
+        if dist is not None and args.full:
             mine = replica_checksum(P).reshape(1)
             allc = [torch.zeros_like(mine) for _ in range(world)]
             if EMULATED:
@@ -907,17 +955,18 @@ def main():
         out["replicas_identical_after_timed_steps"] = replicas_identical
         out["exchange_ms_isolated"] = exch_ms
         out["compute_only_ms_per_step"] = (ms_per_step - exch_ms) if exch_ms is not None else ms_per_step
-        if world == 1 and not FREEZE and not args.train_only and not args.no_config1 and mode != "gaussian-sharded":
+        if (args.full and world == 1 and not FREEZE and not args.train_only and not args.no_config1
+                and mode != "gaussian-sharded"):
             ops.set_gt_moments(ctx, None, None)
             out["config_1"] = config1_bench(ctx, ops, device)
             out["config_1_iters_per_sec"] = out["config_1"]["iters_per_sec"]
-        if world == 1 and not FREEZE and not args.no_scaling_model and mode != "gaussian-sharded":
+        if args.full and world == 1 and not FREEZE and not args.no_scaling_model and mode != "gaussian-sharded":
             out["scaling_model"] = scaling_model(ctx, ops, g_np, w2c_np, Ks_np, N, args.views, W, H, device)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(args)
         else:
             out["cpu_baseline"] = None
-        if world == 1 and not args.train_only:
+        if args.full and world == 1 and not args.train_only:
             out["align"] = align_bench(device, with_cpu=not args.no_cpu_baseline)
             # the synthetic condensed problems at 2 / 8 / 32 views (HIP seconds for 500+200 iterations)
             # (the CPU port beside it at all three sizes; 2 and 32 views on a shorter sample, 50+20 iterations x 10)
@@ -934,7 +983,7 @@ def main():
     # ---- after the line: the whole step under each exchange form of st3r_gs_train_step (a few extra steps each; rs_ag
     # leaves the Adam moments sharded, which no longer matters here).  Every rank arms a watchdog first: the forms other
     # than the plain all-reduce have only ever run with one rank, and a hung collective cannot be interrupted in-process.
-    if dist is not None and mode != "gaussian-sharded" and native_comm and not FREEZE:
+    if args.full and dist is not None and mode != "gaussian-sharded" and native_comm and not FREEZE:
         import threading
         wd = threading.Timer(120.0, lambda: (sys.stderr.write("bench.py: exchange-form timing timed out\n"), os._exit(0)))
         wd.daemon = True; wd.start()
