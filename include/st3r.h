@@ -165,6 +165,19 @@ int st3r_gs_project_sh_bwd(st3r_ctx* ctx, void* stream, int N, int C, const floa
                            float eps2d, const float* splats, const float* v_splats, float reg_views,
                            float opac_fac, float scale_fac, float* grads);
 
+/* gradient of the render loss with respect to each camera's world-to-camera matrix (gsplat's v_viewmats), from the
+ * per-pair gradients v_splats of st3r_gs_blend_bwd; same inputs as st3r_gs_project_sh_bwd (campos = inverse(V)[:3, 3]).
+ * Per visible pair (radius > 0), with p = R m + t, Sigma the world covariance, d = m - campos:
+ *   v_t += v_p    v_R += v_p m^T + 2 v_S R Sigma    v_campos += -v_d
+ * (v_p, v_S: gradients of the camera-space mean and covariance; v_d: of the SH view direction), then per camera
+ *   v_viewmats = [[v_R, v_t], [0, 0]] - (V^-T [v_campos; 0]) (x) inverse(V)[:, 3]
+ * which, like autograd through torch.inverse, has non-zero entries in row 3.  Writes v_viewmats [C,4,4]; sums in
+ * double in a fixed order (no atomics): the same inputs give the same bits. */
+int st3r_gs_viewmat_bwd(st3r_ctx* ctx, void* stream, int N, int C, const float* means, const float* quats,
+                        const float* scales, const float* sh, int sh_stride, const float* viewmats, const float* Ks,
+                        const float* campos, int width, int height, float eps2d, const float* splats,
+                        const float* v_splats, float* v_viewmats);
+
 /* L1 + SSIM of C views (starster/gs.py:126-130; torchmetrics SSIM data_range=1).
  *   loss_c = w_l1 * mean|gt - r| + w_ssim * (1 - SSIM(gt, r))
  * sums [C,2] (double, device): per view  sum|gt-r|  and  sum of the interior SSIM map

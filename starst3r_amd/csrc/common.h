@@ -75,6 +75,7 @@ enum ArenaSlot {
     SLOT_PAIR_TOUCH,  // blend backward -> projection backward: per-pair stamp "some slot of this pair was written" (gs_blend.hip)
     SLOT_KRANGE_PART, // projection: per-block smallest / largest level-1 key (gs_project.hip)
     SLOT_SCAN_CHAIN,  // single-pass scans (gs_isect.hip): ticket, totals, one status word per tile
+    SLOT_POSE_PART,   // pose backward (gs_pose_bwd.hip): one 15-double partial per (camera, block of 256 Gaussians)
     SLOT_COUNT
 };
 

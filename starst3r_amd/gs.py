@@ -190,7 +190,8 @@ def init_3dgs(scene, init_scale=3e-3, lr=1e-3):
 
 
 class _Rasterize(torch.autograd.Function):
-    """Differentiable wrapper so user code can still back-propagate through render_3dgs."""
+    """Differentiable wrapper so user code can still back-propagate through render_3dgs: into the Gaussians and, when
+    w2c requires a gradient, into the camera poses."""
 
     @staticmethod
     def forward(fctx, means, quats, scales, opacities, shN, w2c, Ks, width, height, ctx):
@@ -215,7 +216,12 @@ class _Rasterize(torch.autograd.Function):
         G = ops.split_grads(grads, means.shape[0])
         v_sh = torch.zeros_like(shN)
         v_sh[:, :4] = G["sh"]
-        return G["means"], G["quats"], G["scales"], G["opacities"], v_sh, None, None, None, None, None
+        # camera poses: only when asked for (gsplat's v_viewmats); intrinsics get none, as in gsplat
+        v_w2c = None
+        if fctx.needs_input_grad[5]:
+            v_w2c = ops.viewmat_bwd(ctx, means, quats, scales, shN, w2c, Ks, info["_campos"], W, H, info["_splats"],
+                                    v_splats)
+        return G["means"], G["quats"], G["scales"], G["opacities"], v_sh, v_w2c, None, None, None, None
 
 
 def render_3dgs(scene, w2c: torch.Tensor, intrinsics: torch.Tensor, width: int, height: int):

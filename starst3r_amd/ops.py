@@ -205,6 +205,17 @@ def project_sh_bwd(ctx, means, quats, scales, opacities, sh, viewmats, Ks, campo
     return grads
 
 
+def viewmat_bwd(ctx, means, quats, scales, sh, viewmats, Ks, campos, W, H, splats, v_splats, eps2d=0.3, out=None):
+    """d loss / d viewmats [C,4,4] from the per-pair gradients of blend_bwd (gsplat's v_viewmats), including the
+    view-direction term through campos = inverse(viewmats)[:, :3, 3]."""
+    N, Cn = means.shape[0], viewmats.shape[0]
+    v_viewmats = out if out is not None else torch.empty((Cn, 4, 4), dtype=torch.float32, device=means.device)
+    _lib.check(_lib.lib().st3r_gs_viewmat_bwd(
+        ctx.handle, _stream(), N, Cn, _p(means), _p(quats), _p(scales), _p(sh), sh_stride_of(sh), _p(viewmats),
+        _p(Ks), _p(campos), W, H, eps2d, _p(splats), _p(v_splats), _p(v_viewmats)))
+    return v_viewmats
+
+
 def split_grads(grads, N):
     """views into the block layout means[3N] quats[4N] scales[3N] opacities[N] sh4[12N]"""
     return dict(means=grads[0:3 * N].view(N, 3), quats=grads[3 * N:7 * N].view(N, 4),

@@ -50,8 +50,12 @@ class Scene:
     @property
     def w2c(self) -> torch.Tensor:
         """World-to-camera transformation matrix (inverse of ``c2w``); the reference re-inverts on every
-        access (scene.py:91-95, i.e. every training iteration) -- here the inverse is cached per c2w tensor."""
+        access (scene.py:91-95, i.e. every training iteration) -- here the inverse is cached per c2w tensor.  A c2w that
+        requires a gradient (pose refinement) gets a fresh inverse per access while grad mode is on: every render then
+        has its own autograd node, and several renders may back-propagate before an optimiser step."""
         assert self.c2w is not None, "No c2w matrix available."
+        if self.c2w.requires_grad and torch.is_grad_enabled():
+            return torch.inverse(self.c2w)
         c = self._w2c_cache
         if c is None or c[0] is not self.c2w or c[1] != self.c2w._version:
             self._w2c_cache = (self.c2w, self.c2w._version, torch.inverse(self.c2w))
