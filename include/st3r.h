@@ -178,6 +178,31 @@ int st3r_gs_viewmat_bwd(st3r_ctx* ctx, void* stream, int N, int C, const float* 
                         const float* campos, int width, int height, float eps2d, const float* splats,
                         const float* v_splats, float* v_viewmats);
 
+/* Depth map of a colour render (gsplat render_mode "D"): depth [C,H,W,1],  D(p) = sum_i w_i(p) z_i  with z_i the
+ * camera-space depth of the record (float 9) and w_i = alpha_i T_i the weights st3r_gs_blend_fwd used: same lists, same
+ * exponent arithmetic and tests, and the walk of a pixel ends at last_ids[pixel].  alpha and last_ids are that call's
+ * outputs.  D equals, bit for bit, channel 0 of st3r_gs_blend_fwd on records whose colour is (z, 0, 0). */
+int st3r_gs_blend_depth_fwd(st3r_ctx* ctx, void* stream, int C, int width, int height, int tile_size, int tile_w,
+                            int tile_h, const float* splats, const int32_t* offsets, const int32_t* flatten_ids,
+                            int64_t n_isects, const float* alpha, const int32_t* last_ids, float* depth);
+
+/* Backward of st3r_gs_blend_depth_fwd: v_depth [C,H,W,1] -> v_splats [n_pairs,12], fully written: floats 0-1 (mean2d),
+ * 2 (opacity), 3-5 (conic) and 9 (depth: sum_p w_i v_D), zeros elsewhere.  Like st3r_gs_blend_bwd it must follow
+ * st3r_gs_blend_fwd of the same lists on the same ctx (contribution bitmasks) and sums without atomics in a fixed order
+ * through per-(record, tile) slots of its own: the same inputs give the same bits. */
+int st3r_gs_blend_depth_bwd(st3r_ctx* ctx, void* stream, int C, int width, int height, int tile_size, int tile_w,
+                            int tile_h, const float* splats, const int32_t* offsets, const int32_t* flatten_ids,
+                            int64_t n_isects, const float* alpha, const int32_t* last_ids, const float* v_depth,
+                            const int32_t* cum_tiles, int64_t n_pairs, float* v_splats);
+
+/* The depth column of v_splats into the parameters, z = (R m + t)_z: per visible pair (radius > 0) with
+ * v_z = v_splats[pair, 9]:   v_m += R[2,:] v_z    v_t[2] += v_z    v_R[2,:] += v_z m.
+ * ADDS sum_c R_c[2,:] v_z (cameras in index order) into grads[0 .. 3N) (the means block of st3r_gs_project_sh_bwd's
+ * output) and, unless v_viewmats is NULL, the pose part into row 2 of v_viewmats [C,4,4] (sums in double in a fixed
+ * order, no atomics).  st3r_gs_project_sh_bwd and st3r_gs_viewmat_bwd ignore float 9. */
+int st3r_gs_depth_bwd(st3r_ctx* ctx, void* stream, int N, int C, const float* means, const float* viewmats,
+                      const float* splats, const float* v_splats, float* grads, float* v_viewmats);
+
 /* L1 + SSIM of C views (starster/gs.py:126-130; torchmetrics SSIM data_range=1).
  *   loss_c = w_l1 * mean|gt - r| + w_ssim * (1 - SSIM(gt, r))
  * sums [C,2] (double, device): per view  sum|gt-r|  and  sum of the interior SSIM map

@@ -40,6 +40,9 @@ SIGNATURES = {
     "st3r_gs_project_sh_bwd": [vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, f32, vp, vp, f32, f32,
                                f32, vp],
     "st3r_gs_viewmat_bwd": [vp, vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, f32, vp, vp, vp],
+    "st3r_gs_blend_depth_fwd": [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, i64, vp, vp, vp],
+    "st3r_gs_blend_depth_bwd": [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp],
+    "st3r_gs_depth_bwd": [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp],
     "st3r_loss_l1_ssim": [vp, vp, i32, i32, i32, vp, vp, f32, f32, vp, vp],
     "st3r_loss_gt_moments": [vp, vp, i32, i32, i32, vp, vp],
     "st3r_ctx_set_gt_moments": [vp, vp, vp, i32, i32, i32],

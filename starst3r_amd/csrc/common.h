@@ -76,6 +76,8 @@ enum ArenaSlot {
     SLOT_KRANGE_PART, // projection: per-block smallest / largest level-1 key (gs_project.hip)
     SLOT_SCAN_CHAIN,  // single-pass scans (gs_isect.hip): ticket, totals, one status word per tile
     SLOT_POSE_PART,   // pose backward (gs_pose_bwd.hip): one 15-double partial per (camera, block of 256 Gaussians)
+    SLOT_VTILE_DEPTH, // depth blend backward (gs_blend_depth.hip): its own stamped per-(record, tile) slots, 32 bytes each
+    SLOT_DEPTH_PART,  // depth -> poses (gs_blend_depth.hip): one 4-double partial per (camera, block of 256 Gaussians)
     SLOT_COUNT
 };
 
@@ -120,6 +122,7 @@ struct st3r_ctx {
     // ground-truth moments registered by the caller (st3r_ctx_set_gt_moments, loss.hip): caller-owned, valid until cleared
     const float* gtm_gt; const float* gtm_mom; int gtm_c, gtm_h, gtm_w;
     int bwd_stamp;  // generation stamp of the per-(record, tile) partial-gradient slots
+    int depth_stamp;  // the same for the depth backward's slots (SLOT_VTILE_DEPTH)
     uint32_t scan_gen;   // single-pass scan (gs_isect.hip): generation of its status words
     // record count of the fused steps without a host round trip: sizing hint from the last known count, the read-back
     // still in flight (event), and the capacity the in-flight step was given

@@ -224,24 +224,89 @@ class _Rasterize(torch.autograd.Function):
         return G["means"], G["quats"], G["scales"], G["opacities"], v_sh, v_w2c, None, None, None, None
 
 
-def render_3dgs(scene, w2c: torch.Tensor, intrinsics: torch.Tensor, width: int, height: int):
+RENDER_MODES = ("RGB", "D", "ED", "RGB+D", "RGB+ED")   # gsplat.rasterization's render_mode
+
+
+class _RasterizeDepth(torch.autograd.Function):
+    """_Rasterize plus the depth map of the same render (st3r_gs_blend_depth_fwd): returns (rgb, alpha, depth) and
+    back-propagates from any of them.  The per-pair gradients of the colour and of the depth backward are summed and go
+    through project_sh_bwd / viewmat_bwd once; the depth column (z of the record) is added by st3r_gs_depth_bwd."""
+
+    @staticmethod
+    def forward(fctx, means, quats, scales, opacities, shN, w2c, Ks, width, height, ctx):
+        rgb, alpha, info = ops.rasterization(ctx, means, quats, scales, opacities, shN, w2c, Ks, width, height)
+        depth = ops.blend_depth_fwd(ctx, info["_splats"], info["isect_offsets"], info["_flatten_ids_dense"], alpha,
+                                    info["_last_ids"], w2c.shape[0], width, height)
+        fctx.save_for_backward(means, quats, scales, opacities, shN, w2c, Ks, alpha)
+        fctx.info, fctx.ctx, fctx.wh = info, ctx, (width, height)
+        fctx.set_materialize_grads(False)   # an output the loss does not use costs no backward kernel
+        return rgb, alpha, depth
+
+    @staticmethod
+    def backward(fctx, v_rgb, v_alpha, v_depth):
+        means, quats, scales, opacities, shN, w2c, Ks, alpha = fctx.saved_tensors
+        info, ctx, (W, H) = fctx.info, fctx.ctx, fctx.wh
+        Cn, N = w2c.shape[0], means.shape[0]
+        lists = (info["_splats"], info["isect_offsets"], info["_flatten_ids_dense"])
+        # both backward kernels consume the contribution masks of THIS rasterization (see _Rasterize.backward)
+        ops.blend_fwd(ctx, *lists, Cn, W, H)
+        v_splats = None
+        if v_rgb is not None or v_alpha is not None:
+            v_rgb = torch.zeros((Cn, H, W, 3), device=alpha.device) if v_rgb is None else v_rgb.contiguous().float()
+            v_splats = ops.blend_bwd(ctx, *lists, alpha, info["_last_ids"], v_rgb,
+                                     None if v_alpha is None else v_alpha.contiguous().float(), info["_cum_tiles"], Cn, W, H)
+        if v_depth is not None:
+            v_d = ops.blend_depth_bwd(ctx, *lists, alpha, info["_last_ids"], v_depth.contiguous().float(),
+                                      info["_cum_tiles"], Cn, W, H)
+            v_splats = v_d if v_splats is None else v_splats.add_(v_d)   # (disjoint: colour floats 6-8, depth float 9)
+        if v_splats is None:
+            v_splats = torch.zeros_like(info["_splats"])
+        grads = ops.project_sh_bwd(ctx, means, quats, scales, opacities, shN, w2c, Ks, info["_campos"], W, H,
+                                   info["_splats"], v_splats)
+        v_w2c = None
+        if fctx.needs_input_grad[5]:
+            v_w2c = ops.viewmat_bwd(ctx, means, quats, scales, shN, w2c, Ks, info["_campos"], W, H, info["_splats"],
+                                    v_splats)
+        if v_depth is not None:
+            ops.depth_bwd(ctx, means, w2c, info["_splats"], v_splats, grads, v_w2c)
+        G = ops.split_grads(grads, N)
+        v_sh = torch.zeros_like(shN)
+        v_sh[:, :4] = G["sh"]
+        return G["means"], G["quats"], G["scales"], G["opacities"], v_sh, v_w2c, None, None, None, None
+
+
+def render_3dgs(scene, w2c: torch.Tensor, intrinsics: torch.Tensor, width: int, height: int, render_mode: str = "RGB"):
     """Render the splats from a set of camera views (reference gs.py:47-88).
 
     Returns the tuple the reference gets from gsplat.rasterization: (render_img (N,H,W,3),
-    render_alpha (N,H,W,1), info)."""
+    render_alpha (N,H,W,1), info).  render_mode follows gsplat: "D" (accumulated depth sum_i w_i z_i) and "ED"
+    (expected depth D / clamp(alpha, min=1e-10)) return render_img (N,H,W,1); "RGB+D" and "RGB+ED" return (N,H,W,4)
+    with the depth last.  Every mode back-propagates into the Gaussians and, when it requires a gradient, into w2c."""
+    if render_mode not in RENDER_MODES:
+        raise ValueError(f"render_mode must be one of {RENDER_MODES}, got {render_mode!r}")
     g = scene.gaussians
     ctx = ops.get_context(scene.device)
     w2c = w2c.to(scene.device, torch.float32).contiguous(); Ks = intrinsics.to(scene.device, torch.float32).contiguous()
-    rgb, alpha = _Rasterize.apply(g["means"], g["quats"], g["scales"], g["opacities"], g["shN"], w2c, Ks, width,
-                                  height, ctx)
+    if render_mode == "RGB":
+        rgb, alpha = _Rasterize.apply(g["means"], g["quats"], g["scales"], g["opacities"], g["shN"], w2c, Ks, width,
+                                      height, ctx)
+        img = rgb
+    else:
+        rgb, alpha, depth = _RasterizeDepth.apply(g["means"], g["quats"], g["scales"], g["opacities"], g["shN"], w2c, Ks,
+                                                  width, height, ctx)
+        if render_mode.endswith("ED"):
+            depth = depth / alpha.clamp(min=1e-10)
+        img = torch.cat([rgb, depth], dim=-1) if render_mode.startswith("RGB") else depth
     # the info dict of the most recent rasterization (gsplat's `meta`)
     info = {k: v for k, v in ops.last_info().items() if not k.startswith("_")}
-    return rgb, alpha, info
+    return img, alpha, info
 
 
-def render_3dgs_original(scene, width: int, height: int):
+def render_3dgs_original(scene, width: int, height: int, render_mode: str = "RGB"):
     """Render from camera views of original scene (reference gs.py:90-95)."""
-    return scene.render_3dgs(scene.w2c, scene.intrinsics, width, height)
+    if render_mode == "RGB":
+        return scene.render_3dgs(scene.w2c, scene.intrinsics, width, height)
+    return scene.render_3dgs(scene.w2c, scene.intrinsics, width, height, render_mode=render_mode)
 
 
 def _gt_on_device(scene, views):

@@ -194,6 +194,35 @@ def blend_bwd(ctx, splats, off, flat, alpha, last, v_rgb, v_alpha, cum, Cn, W, H
     return v_splats
 
 
+def blend_depth_fwd(ctx, splats, off, flat, alpha, last, Cn, W, H):
+    """Depth map [Cn,H,W,1] with the weights of the blend_fwd call that returned (alpha, last)."""
+    tw, th = tile_grid(W, H)
+    depth = torch.empty((Cn, H, W, 1), dtype=torch.float32, device=splats.device)
+    _lib.check(_lib.lib().st3r_gs_blend_depth_fwd(ctx.handle, _stream(), Cn, W, H, TILE, tw, th, _p(splats),
+                                                  _p(off, torch.int32), _p(flat, torch.int32), flat.numel(), _p(alpha),
+                                                  _p(last, torch.int32), _p(depth)))
+    return depth
+
+
+def blend_depth_bwd(ctx, splats, off, flat, alpha, last, v_depth, cum, Cn, W, H):
+    """Per-pair gradients of the depth map (floats 0-5 and 9 of v_splats); must follow blend_fwd of the same lists."""
+    tw, th = tile_grid(W, H)
+    v_splats = torch.empty_like(splats)
+    _lib.check(_lib.lib().st3r_gs_blend_depth_bwd(ctx.handle, _stream(), Cn, W, H, TILE, tw, th, _p(splats),
+                                                  _p(off, torch.int32), _p(flat, torch.int32), flat.numel(), _p(alpha),
+                                                  _p(last, torch.int32), _p(v_depth), _p(cum, torch.int32),
+                                                  splats.shape[0], _p(v_splats)))
+    return v_splats
+
+
+def depth_bwd(ctx, means, viewmats, splats, v_splats, grads, v_viewmats=None):
+    """Adds the depth column of v_splats into grads[0:3N] (means) and, if given, into v_viewmats [Cn,4,4]."""
+    N, Cn = means.shape[0], viewmats.shape[0]
+    _lib.check(_lib.lib().st3r_gs_depth_bwd(ctx.handle, _stream(), N, Cn, _p(means), _p(viewmats), _p(splats),
+                                            _p(v_splats), _p(grads), _p(v_viewmats)))
+    return grads, v_viewmats
+
+
 def project_sh_bwd(ctx, means, quats, scales, opacities, sh, viewmats, Ks, campos, W, H, splats, v_splats,
                    reg_views=0.0, opac_fac=0.0, scale_fac=0.0, eps2d=0.3, out=None):
     N, Cn = means.shape[0], viewmats.shape[0]

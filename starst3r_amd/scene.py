@@ -80,11 +80,15 @@ class Scene:
     def init_3dgs(self, init_scale=3e-3, lr=1e-3):
         _gs.init_3dgs(self, init_scale, lr)
 
-    def render_3dgs(self, w2c, intrinsics, width, height):
-        return _gs.render_3dgs(self, w2c, intrinsics, width, height)
+    def render_3dgs(self, w2c, intrinsics, width, height, render_mode="RGB"):
+        if render_mode == "RGB":   # the reference's call, argument for argument
+            return _gs.render_3dgs(self, w2c, intrinsics, width, height)
+        return _gs.render_3dgs(self, w2c, intrinsics, width, height, render_mode=render_mode)
 
-    def render_3dgs_original(self, width, height):
-        return _gs.render_3dgs_original(self, width, height)
+    def render_3dgs_original(self, width, height, render_mode="RGB"):
+        if render_mode == "RGB":
+            return _gs.render_3dgs_original(self, width, height)
+        return _gs.render_3dgs_original(self, width, height, render_mode=render_mode)
 
     def run_3dgs_optim(self, iters: int, enable_pruning: bool = False, loss_ssim_fac=0.2, loss_opacity_fac=0.01,
                        loss_scale_fac=0.01, verbose: bool = False) -> list:
