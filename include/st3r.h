@@ -472,6 +472,46 @@ int st3r_gs_train_step(st3r_ctx* ctx, void* stream, int N, int C, float* means, 
                        double beta2, double eps, int step, float* loss_out, int64_t* stats_host);
 
 /* ----------------------------------------------------------------------------------
+ * Camera poses inside the training step (joint refinement of the cameras the alignment produced).
+ *
+ * st3r_pose_adam_step: one Adam step on the C world-to-camera matrices viewmats [C,4,4] (in/out) from their gradient
+ * v_viewmats [C,4,4] (st3r_gs_viewmat_bwd), on the device, in double.  Per camera, V = [R t; 0 1], G = v_viewmats[c]
+ * (row 3 of G is ignored: the bottom row of a rigid V is not varied); left perturbation V <- exp(xi^) V,
+ * xi = (omega, upsilon):
+ *     A = G[:3,:3] R^T     g_omega = (A21 - A12, A02 - A20, A10 - A01) + t x G[:3,3]     g_upsilon = G[:3,3]
+ *   Adam on the six scalars (torch's formulas, bias corrected by the 1-based `step`; moments pose_m / pose_v [6C],
+ *   omega first):  delta = -lr mhat / (sqrt(vhat) + eps)
+ *   R' = Rodrigues(delta_omega) R,  t' = Rodrigues(delta_omega) t + delta_upsilon,  Gram-Schmidt on the rows of R'
+ *   (row 0 normalised, row 1 minus its projection then normalised, row 2 = row 0 x row 1),  campos' = -R'^T t'
+ * viewmats (bottom row written 0 0 0 1), campos [C,3] (in/out) and the moments are stored as float32.  mask (may be
+ * NULL): [C] floats, a camera with mask[c] == 0 is skipped whole -- V, campos, m, v keep their bits.  Like
+ * st3r_adam_step the update is guarded on the device by the record count of an asynchronous training step still in
+ * flight: a step that outgrew its buffers moves no camera.
+ *
+ * st3r_gs_train_step_poses: st3r_gs_train_step on a single replica, plus the cameras: forward, loss, backward ->
+ * Gaussian gradients and v_viewmats (both at the poses the call started with) -> Gaussian Adam -> pose Adam
+ * (pose_lr, the Gaussians' betas and eps, pose_step, pose_mask as above), all on `stream` with no host round trip
+ * of its own (stats_host == NULL: asynchronous in steady state; the capacity / repeat protocol of
+ * st3r_gs_train_fwd_bwd holds, and a repeated step has moved nothing).  The per-pair gradients of the pose
+ * backward are the in-order sums of the blend backward's (record, tile) slots, materialised by the kernel that
+ * serves st3r_gs_blend_bwd, and reduced by st3r_gs_viewmat_bwd's kernels: fixed order, double partials, no float
+ * atomics -- the same inputs give the same bits, and grads[23N] is bit-identical to st3r_gs_train_step's.  In a
+ * chunked-view call a camera's gradient comes from its own chunk and its update runs once, after the last chunk.
+ * v_viewmats_out (may be NULL): [C,4,4], this step's pose gradient (tests, diagnostics).  With a communicator
+ * attached the call returns ST3R_ERR_INVALID: view-sharded pose training is not supported.
+ * ---------------------------------------------------------------------------------- */
+int st3r_pose_adam_step(st3r_ctx* ctx, void* stream, int C, float* viewmats, float* campos, const float* v_viewmats,
+                        float* pose_m, float* pose_v, double lr, double beta1, double beta2, double eps, int step,
+                        const float* mask);
+int st3r_gs_train_step_poses(st3r_ctx* ctx, void* stream, int N, int C, float* means, float* quats, float* scales,
+                             float* opacities, float* sh, int sh_stride, float* viewmats, const float* Ks,
+                             float* campos, const float* gt_images, int width, int height, float ssim_fac,
+                             float opac_fac, float scale_fac, float* grads, float* m, float* v, double lr, double beta1,
+                             double beta2, double eps, int step, float* loss_out, int64_t* stats_host, float* pose_m,
+                             float* pose_v, double pose_lr, int pose_step, const float* pose_mask,
+                             float* v_viewmats_out);
+
+/* ----------------------------------------------------------------------------------
  * Dense point extraction between alignment and 3DGS seeding: what
  * starster/scene.py:148 takes from `scene.get_dense_pts3d(clean_depth=True)` (Mast3r SparseGA [U]).
  * Views are concatenated; view v owns the dense pixels [view_start[v], view_start[v+1]) in raster order.

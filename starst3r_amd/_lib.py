@@ -73,6 +73,9 @@ SIGNATURES = {
     "st3r_grad_allreduce": [vp, vp, vp, i64],
     "st3r_gs_train_step": [vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, i32, f32, f32, f32, vp, vp,
                            vp, f64, f64, f64, f64, i32, vp, C.POINTER(i64)],
+    "st3r_pose_adam_step": [vp, vp, i32, vp, vp, vp, vp, vp, f64, f64, f64, f64, i32, vp],
+    "st3r_gs_train_step_poses": [vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, i32, f32, f32, f32, vp,
+                                 vp, vp, f64, f64, f64, f64, i32, vp, C.POINTER(i64), vp, vp, f64, i32, vp, vp],
     "st3r_recip_nn_seed_count": [i32, i32, i32],
     "st3r_recip_nn": [vp, vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp],
     "st3r_dense_unproject": [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp],

@@ -220,6 +220,7 @@ int st3r_project_sh_bwd_impl(hipStream_t s, int N, int C, const float* means, co
                              const st3r_vtile_ref* slots);
 int st3r_loss_impl(st3r_ctx* ctx, hipStream_t s, int C, int H, int W, const float* render, const float* gt,
                    float w_l1, float w_ssim, double* sums, float* v_render, bool sums_cleared);
+int st3r_gather_vtile_impl(hipStream_t s, int64_t n_pairs, const st3r_vtile_ref* slots, float* v_splats);
 
 static int bit_length_u32(uint32_t v) { int n = 0; while (v) { ++n; v >>= 1; } return n; }
 
@@ -451,11 +452,16 @@ __global__ void k_finalize_loss(int C, const double* __restrict__ sums, const do
 
 // The views [c0, c0 + C) of one training call: rasterize -> loss -> backward; the parameter gradients are written
 // (accumulate = false) or added (later view chunks of the same call).
+// v_viewmats != NULL (st3r_gs_train_step_poses): the gradient of these views' world-to-camera matrices is written as well,
+// [C,4,4], by two launches BEHIND the ones of a call without it: k_gather_vtile materialises the per-pair sums of the
+// backward's slots (the projection backward above summed the same slots itself and is left as it is) and
+// st3r_gs_viewmat_bwd reduces them per camera -- the stand-alone pose backward, unchanged, so the fused gradient is the
+// unfused one.
 static int train_views(st3r_ctx* ctx, hipStream_t s, int N, int C, const float* means, const float* quats,
                        const float* scales, const float* opacities, const float* sh, int sh_stride,
                        const float* viewmats, const float* Ks, const float* campos, const float* gt_images, int W, int H,
                        float ssim_fac, float opac_fac, float scale_fac, double* sums, double* reg_sums, bool allow_async,
-                       bool accumulate, float* grads, RasterOut* ro_out) {
+                       bool accumulate, float* grads, RasterOut* ro_out, float* v_viewmats = nullptr) {
     const int64_t n_pairs = (int64_t)N * C, n_px = (int64_t)C * H * W;
     RasterOut ro;
     int rc = rasterize_front(ctx, s, N, C, means, quats, scales, opacities, sh, sh_stride, viewmats, Ks, campos, W, H,
@@ -516,15 +522,23 @@ static int train_views(st3r_ctx* ctx, hipStream_t s, int N, int C, const float* 
     }
     st3r_prof_end(ctx, s, STG_PROJECT_BWD);
     *ro_out = ro;
+    if (!rc && v_viewmats) {
+        GET(SLOT_VSPLATS, float, n_pairs * ST3R_SPLAT_STRIDE, v_pairs);
+        rc = st3r_gather_vtile_impl(s, n_pairs, slots, v_pairs);
+        if (!rc)
+            rc = st3r_gs_viewmat_bwd(ctx, s, N, C, means, quats, scales, sh, sh_stride, viewmats, Ks, campos, W, H, 0.3f,
+                                     ro.splats, v_pairs, v_viewmats);
+    }
     return rc;
 }
 
-ST3R_EXPORT int st3r_gs_train_fwd_bwd(st3r_ctx* ctx, void* stream, int N, int C, const float* means,
-                                      const float* quats, const float* scales, const float* opacities,
-                                      const float* sh, int sh_stride, const float* viewmats, const float* Ks,
-                                      const float* campos, const float* gt_images, int width, int height,
-                                      float ssim_fac, float opac_fac, float scale_fac, float* grads,
-                                      float* loss_out, int64_t* stats_host) {
+// st3r_gs_train_fwd_bwd, and with v_viewmats != NULL ([C,4,4]) the pose gradient of every view next to it: a view belongs
+// to one chunk of a chunked call, which writes that view's matrix.
+int st3r_train_fwd_bwd_impl(st3r_ctx* ctx, void* stream, int N, int C, const float* means, const float* quats,
+                            const float* scales, const float* opacities, const float* sh, int sh_stride,
+                            const float* viewmats, const float* Ks, const float* campos, const float* gt_images, int width,
+                            int height, float ssim_fac, float opac_fac, float scale_fac, float* grads, float* loss_out,
+                            int64_t* stats_host, float* v_viewmats) {
     ARG_CHECK(ctx && N > 0 && C > 0 && C <= ST3R_MAX_VIEWS && width > 0 && height > 0 && sh_stride >= 12);
     ARG_CHECK((int64_t)N * C < 2147483647LL);   // pair ids, tile counts and their scans are int32
     ARG_CHECK(means && quats && scales && opacities && sh && viewmats && Ks && campos && gt_images && grads && loss_out);
@@ -559,7 +573,7 @@ ST3R_EXPORT int st3r_gs_train_fwd_bwd(st3r_ctx* ctx, void* stream, int N, int C,
             rc = train_views(ctx, s, N, c1 - c0, means, quats, scales, opacities, sh, sh_stride, viewmats + 16 * c0,
                              Ks + 9 * c0, campos + 3 * c0, gt_images + (int64_t)c0 * H * W * 3, W, H, ssim_fac, opac_fac,
                              scale_fac, sums + 2 * c0, rs, stats_host == nullptr && chunks == 1 && !ctx->comm, !first, grads,
-                             &ro);
+                             &ro, v_viewmats ? v_viewmats + 16 * c0 : nullptr);
             if (!rc) { st_vis += ro.n_visible; st_is += ro.n_records; st_ref += ro.n_isects_ref; }
             first = false;
         }
@@ -584,6 +598,17 @@ ST3R_EXPORT int st3r_gs_train_fwd_bwd(st3r_ctx* ctx, void* stream, int N, int C,
         stats_host[3] = st_ref;   // exact: stats_host selects the synchronous path
     }
     return ST3R_OK;
+}
+
+ST3R_EXPORT int st3r_gs_train_fwd_bwd(st3r_ctx* ctx, void* stream, int N, int C, const float* means,
+                                      const float* quats, const float* scales, const float* opacities,
+                                      const float* sh, int sh_stride, const float* viewmats, const float* Ks,
+                                      const float* campos, const float* gt_images, int width, int height,
+                                      float ssim_fac, float opac_fac, float scale_fac, float* grads,
+                                      float* loss_out, int64_t* stats_host) {
+    return st3r_train_fwd_bwd_impl(ctx, stream, N, C, means, quats, scales, opacities, sh, sh_stride, viewmats, Ks, campos,
+                                   gt_images, width, height, ssim_fac, opac_fac, scale_fac, grads, loss_out, stats_host,
+                                   nullptr);
 }
 
 // Gaussian-sharded multi-GPU mode, middle phase: this rank owns C views and received the splat records of ALL

@@ -44,7 +44,7 @@ enum ArenaSlot {
     SLOT_ALPHA,
     SLOT_LAST,
     SLOT_VRENDER,
-    SLOT_VSPLATS,
+    SLOT_VSPLATS,     // fused step with poses: the per-pair gradients k_gather_vtile materialises for the pose backward
     SLOT_SSIM_A,
     SLOT_SORT_TMP,
     SLOT_SCAN_TMP,
@@ -78,6 +78,7 @@ enum ArenaSlot {
     SLOT_POSE_PART,   // pose backward (gs_pose_bwd.hip): one 15-double partial per (camera, block of 256 Gaussians)
     SLOT_VTILE_DEPTH, // depth blend backward (gs_blend_depth.hip): its own stamped per-(record, tile) slots, 32 bytes each
     SLOT_DEPTH_PART,  // depth -> poses (gs_blend_depth.hip): one 4-double partial per (camera, block of 256 Gaussians)
+    SLOT_POSE_GRAD,   // fused step with poses (gs_pose_step.hip): v_viewmats [C,4,4] of the step when the caller wants no copy
     SLOT_COUNT
 };
 

@@ -693,6 +693,17 @@ int st3r_blend_bwd_impl(st3r_ctx* ctx, hipStream_t s, int C, int W, int H, int t
     return ST3R_OK;
 }
 
+// The per-pair sums of a deferred backward (defer != NULL above), materialised after all: the fused step with poses
+// (gs_pose_step.hip) feeds them to the pose backward.  The same kernel, the same slots, the same order as the
+// stand-alone st3r_gs_blend_bwd.
+int st3r_gather_vtile_impl(hipStream_t s, int64_t n_pairs, const st3r_vtile_ref* slots, float* v_splats) {
+    if (n_pairs <= 0) return ST3R_OK;
+    hipLaunchKernelGGL(k_gather_vtile, dim3(ceil_div(n_pairs, 256)), dim3(256), 0, s, n_pairs, slots->cum, slots->vtile,
+                       slots->stamp, slots->vt_cap, (float4*)v_splats);
+    LAUNCH_CHECK();
+    return ST3R_OK;
+}
+
 ST3R_EXPORT int st3r_gs_blend_bwd(st3r_ctx* ctx, void* stream, int C, int width, int height, int tile_size,
                                   int tile_w, int tile_h, const float* splats, const int32_t* offsets,
                                   const int32_t* flatten_ids, int64_t n_isects, const float* alpha,

@@ -335,13 +335,28 @@ def run_3dgs_optim(
         loss_opacity_fac=0.01,
         loss_scale_fac=0.01,
         verbose: bool = False,
+        pose_lr=0.0,
+        pose_freeze=(),
     ) -> list:
     """Run 3DGS optimization and pruning (optional) for a number of iterations (reference gs.py:97-166).
 
     Returns the list of per-iteration losses (floats).  Under torch.distributed (one process per GPU, RCCL)
     the views are sharded over the ranks, the [23N] gradient buffer is sum-all-reduced every iteration and
     every rank applies the identical fused Adam update; the returned losses are the sums over all views.
+
+    pose_lr (not in the reference; a float or a callable step -> float): when not 0.0 the cameras are optimised jointly
+    with the Gaussians, inside the same fused step (Adam on a left se(3) perturbation of every world-to-camera matrix,
+    ops.train_step_poses); the views listed in pose_freeze stay fixed.  A callable receives the iteration index of THIS
+    call (0 .. iters-1), like the returned losses -- a second call restarts the schedule, while the pose moments and
+    their step counter (bias correction) continue.  The loop trains a private copy of the poses; when
+    it ends scene.c2w is REPLACED by a new tensor, the inverse of the refined matrices (frozen views keep their rows bit
+    for bit).  The pose moments and step counter persist on scene._gs_optim like the Gaussians'.  Single process,
+    Gaussians replicated only.
     """
+    poses_on = callable(pose_lr) or float(pose_lr) != 0.0
+    if poses_on and (_dist.rank_world()[1] > 1 or _sharded_layout(scene, 1, enable_pruning)):
+        raise NotImplementedError("pose_lr != 0 is supported in a single process with replicated Gaussians only "
+                                  "(not under torch.distributed, not with ST3R_MULTI_GPU=gaussian-sharded)")
     height, width = scene.imgs[0].shape[:2]
     ctx = ops.get_context(scene.device)
     st = scene._gs_optim
@@ -358,6 +373,18 @@ def run_3dgs_optim(
     gt = _gt_on_device(scene, views)
     losses = torch.zeros(max(iters, 1), device=scene.device)
     fused = world == 1 or getattr(ctx, "native_comm", False)
+    if poses_on:
+        # a private copy: the tensor Scene.w2c caches is never trained (w2c_all may BE that tensor)
+        w2c = w2c.clone()
+        n_cam = w2c.shape[0]
+        if getattr(st, "pose_m", None) is None or st.pose_m.numel() != 6 * n_cam:   # first use, or the views changed
+            st.pose_m = torch.zeros(6 * n_cam, device=w2c.device); st.pose_v = torch.zeros_like(st.pose_m)
+            st.pose_step = 0
+        frozen = sorted({int(i) % n_cam for i in pose_freeze})
+        pose_mask = torch.ones(n_cam, device=w2c.device)
+        if frozen:
+            pose_mask[frozen] = 0.0
+        st.pose_w2c = w2c   # the matrices being trained (diagnostics; scene.c2w follows when the loop ends)
     restore_exchange = None
     if enable_pruning and fused and world > 1 and ops.get_exchange(ctx) in ("rs_ag", "direct"):
         # reduce-scatter exchange (through RCCL or through the peers' exported buffers): a rank maintains the Adam moments of its piece of the buffer only; growing the set
@@ -384,7 +411,13 @@ def run_3dgs_optim(
             sh_c[0] = g["shN"].data[:, :4].contiguous()
         P = {k: g[k].data for k in ("means", "quats", "scales", "opacities")}  # growth replaces the tensors
         P["shN"] = sh_c[0]
-        if fused:   # the whole iteration is one C call (gradient all-reduce inside, over the ctx's communicator)
+        if poses_on:   # the same single call, and the cameras move in it too (w2c and campos in place)
+            ops.train_step_poses(ctx, P, w2c, Ks, campos, gt, width, height, loss_ssim_fac, loss_opacity_fac,
+                                 loss_scale_fac, st.grads, st.m, st.v, st.lr, st.betas[0], st.betas[1], st.eps, st.step,
+                                 losses[step:step + 1], st.pose_m, st.pose_v,
+                                 float(pose_lr(step)) if callable(pose_lr) else float(pose_lr), st.pose_step, pose_mask,
+                                 want_stats=False)
+        elif fused:   # the whole iteration is one C call (gradient all-reduce inside, over the ctx's communicator)
             # no host round trip in steady state (single rank; with a communicator the library sizes every step exactly)
             ops.train_step(ctx, P, w2c, Ks, campos, gt, width, height, loss_ssim_fac, loss_opacity_fac,
                            loss_scale_fac, st.grads, st.m, st.v, st.lr, st.betas[0], st.betas[1], st.eps, st.step,
@@ -398,6 +431,11 @@ def run_3dgs_optim(
 
     def capacity_error(e):
         return getattr(e, "code", 0) == -3 and world == 1
+
+    def count_step(d):   # the pose step counter moves wherever the Gaussians' does
+        st.step += d
+        if poses_on:
+            st.pose_step += d
 
     # A peer failure (ST3R_ERR_PEER: the step before failed on some rank, nobody applied it) ABORTS the run on every rank
     # alike -- all ranks get the code from the same call --; the exchange form is restored whatever ends the loop.
@@ -414,7 +452,7 @@ def run_3dgs_optim(
                 scene.strategy.step_pre_backward(g, scene.optimizers, scene.strategy_state, step, None)
                 if not own_strategy:
                     sh_c[0] = g["shN"].data[:, :4].contiguous()
-            st.step += 1
+            count_step(1)
             try:
                 one_iteration(step)
             except _lib_mod.St3rError as e:
@@ -426,13 +464,14 @@ def run_3dgs_optim(
                 # (its position noise, and on a refinement step its relocation / growth): they are NOT run again, i.e. the
                 # noise of that one iteration is drawn before its update instead of after it.  A deviation of one step's
                 # noise (tests/test_gpu_api.py::test_run_3dgs_optim_repeats_...); overflows need > 25 % more tile
-                # intersections than the step before.
+                # intersections than the step before.  With pose_lr != 0 the cameras of the lost iteration did not move
+                # either (the pose update carries the same guard).
                 if not capacity_error(e):
                     raise
                 if step > 0:
-                    st.step -= 1
+                    count_step(-1)
                     one_iteration(step - 1)
-                    st.step += 1
+                    count_step(1)
                 one_iteration(step)
             if enable_pruning:
                 touch = bool(scene.strategy.is_refine_step(step)) if own_strategy else True
@@ -455,6 +494,13 @@ def run_3dgs_optim(
             sh_write_back()
         if restore_exchange is not None:   # (the moments stay complete on every rank: rs_ag goes on using its own piece)
             ops.set_exchange(ctx, restore_exchange)
+        if poses_on:
+            # a NEW c2w tensor, so that Scene.w2c's cache refreshes itself; inverted in double, device and dtype as before
+            old = scene.c2w
+            c2w = torch.inverse(w2c.double()).to(device=old.device, dtype=old.dtype)
+            if frozen:
+                c2w[frozen] = old.detach()[frozen]
+            scene.c2w = c2w
     _dist.all_reduce_sum(losses)
     return losses[:iters].cpu().tolist()   # one device->host copy for the whole call (reference: .item() per step)
 

@@ -344,6 +344,35 @@ def train_step(ctx, params, viewmats, Ks, campos, gt, W, H, ssim_fac, opac_fac, 
     return dict(n_visible=int(stats[0]), n_isects=int(stats[1]), arena_bytes=int(stats[2]), n_isects_ref=int(stats[3]))
 
 
+def pose_adam_step(ctx, viewmats, campos, v_viewmats, pose_m, pose_v, lr, b1, b2, eps, step, mask=None):
+    """One Adam step on the cameras, in place: viewmats [C,4,4], campos [C,3], moments pose_m / pose_v [6C] (omega first),
+    from v_viewmats [C,4,4]; left perturbation exp(xi^) V, rows re-orthonormalised (st3r_pose_adam_step).  mask [C]
+    floats or None: cameras with mask == 0 keep every bit."""
+    Cn = viewmats.shape[0]
+    _lib.check(_lib.lib().st3r_pose_adam_step(ctx.handle, _stream(), Cn, _p(viewmats), _p(campos), _p(v_viewmats),
+                                              _p(pose_m), _p(pose_v), lr, b1, b2, eps, step, _p(mask)))
+
+
+def train_step_poses(ctx, params, viewmats, Ks, campos, gt, W, H, ssim_fac, opac_fac, scale_fac, grads, m, v, lr, b1, b2,
+                     eps, step, loss_out, pose_m, pose_v, pose_lr, pose_step, pose_mask=None, v_viewmats_out=None,
+                     want_stats=True):
+    """train_step on a single replica that also moves the cameras: viewmats and campos are updated IN PLACE by one Adam
+    step (pose_lr, the Gaussians' betas and eps, pose_step; moments pose_m / pose_v [6C]) after the Gaussians' update; both
+    gradients belong to the poses the call started with.  pose_mask [C] floats: 0 freezes a camera.  v_viewmats_out
+    [C,4,4]: receives this step's pose gradient.  want_stats as in train_step."""
+    N, Cn = params["means"].shape[0], viewmats.shape[0]
+    sh = params["shN"]
+    stats = (C.c_int64 * 4)() if want_stats else None
+    _lib.check(_lib.lib().st3r_gs_train_step_poses(
+        ctx.handle, _stream(), N, Cn, _p(params["means"]), _p(params["quats"]), _p(params["scales"]),
+        _p(params["opacities"]), _p(sh), sh_stride_of(sh), _p(viewmats), _p(Ks), _p(campos), _p(gt), W, H, ssim_fac,
+        opac_fac, scale_fac, _p(grads), _p(m), _p(v), lr, b1, b2, eps, step, _p(loss_out), stats, _p(pose_m), _p(pose_v),
+        pose_lr, pose_step, _p(pose_mask), _p(v_viewmats_out)))
+    if not want_stats:
+        return None
+    return dict(n_visible=int(stats[0]), n_isects=int(stats[1]), arena_bytes=int(stats[2]), n_isects_ref=int(stats[3]))
+
+
 def dense_unproject(ctx, view_start, pixels, idxs, offsets, core, cam_rows, base_focals):
     """All dense pixels of all views (concatenated) -> world points [n,3] and own-camera depth [n]."""
     n, Cn, G = pixels.shape[0], cam_rows.shape[0], core.shape[1]

@@ -91,6 +91,9 @@ class Scene:
         return _gs.render_3dgs_original(self, width, height, render_mode=render_mode)
 
     def run_3dgs_optim(self, iters: int, enable_pruning: bool = False, loss_ssim_fac=0.2, loss_opacity_fac=0.01,
-                       loss_scale_fac=0.01, verbose: bool = False) -> list:
+                       loss_scale_fac=0.01, verbose: bool = False, pose_lr=0.0, pose_freeze=()) -> list:
+        if not callable(pose_lr) and float(pose_lr) == 0.0 and not tuple(pose_freeze):   # the reference's call
+            return _gs.run_3dgs_optim(self, iters, enable_pruning, loss_ssim_fac, loss_opacity_fac, loss_scale_fac,
+                                      verbose)
         return _gs.run_3dgs_optim(self, iters, enable_pruning, loss_ssim_fac, loss_opacity_fac, loss_scale_fac,
-                                  verbose)
+                                  verbose, pose_lr=pose_lr, pose_freeze=pose_freeze)
