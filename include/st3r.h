@@ -222,6 +222,34 @@ int st3r_loss_l1_ssim(st3r_ctx* ctx, void* stream, int C, int height, int width,
 int st3r_loss_gt_moments(st3r_ctx* ctx, void* stream, int C, int height, int width, const float* gt, float* moments);
 int st3r_ctx_set_gt_moments(st3r_ctx* ctx, const float* gt, const float* moments, int C, int height, int width);
 
+/* Depth-prior loss of C views: a weighted L1 between the expected depth of a render and a per-pixel prior.
+ * depth, alpha [C,H,W,1]: D and alpha of the render (st3r_gs_blend_depth_fwd, st3r_gs_blend_fwd); prior, weight [C,H,W],
+ * weight >= 0.
+ *   ED = D / max(alpha, 1e-10)     n_c = max(sum_p w_c, 1)     loss_c = depth_fac * sum_p w_c |ED - Z_c| / n_c
+ * sums [C,2] (double, device; written): per view  sum_p w |ED - Z|  and  n_c, so loss_c = depth_fac sums[c,0] / sums[c,1].
+ * v_depth, v_alpha [C,H,W,1] (written) = d(sum_c loss_c)/dD, /dalpha; v_alpha is the derivative through ED and is zero
+ * where alpha < 1e-10 (torch's clamp gradient).  A pixel with w == 0 contributes nothing and gets zero gradients whatever
+ * D, alpha and Z hold there (NaN and inf included).  Sums in double in a fixed order, no atomics: the same inputs give
+ * the same bits. */
+int st3r_loss_depth_prior(st3r_ctx* ctx, void* stream, int C, int height, int width, const float* depth,
+                          const float* alpha, const float* prior, const float* weight, float depth_fac, double* sums,
+                          float* v_depth, float* v_alpha);
+
+/* Registers a depth prior for the images at `gt` [C,H,W,3]: depth, weight [C,H,W] as above.  From then on
+ * st3r_gs_train_fwd_bwd / _step / _step_poses add the term above to their loss whenever their ground-truth pointer is
+ * `gt` or a whole-view offset into it (view chunks) with the same height and width and depth_fac != 0: the step renders
+ * the depth map of its own lists (st3r_gs_blend_depth_fwd), takes this loss, hands v_alpha to the colour backward, runs
+ * st3r_gs_blend_depth_bwd, feeds the SUM of both per-pair gradient arrays to the projection backward and adds the depth
+ * column with st3r_gs_depth_bwd (means; in _step_poses row 2 of the pose gradient as well) -- the kernels and the order
+ * of the unfused chain, so the same bits.  loss_out includes sum_c loss_c.  n_c is computed once per registration, by the
+ * first call that uses it and on that call's stream: the training calls of one registration must run on ONE stream (or
+ * be ordered behind that first call by the caller).  With no registration, or depth_fac == 0, every call runs exactly the launches it ran before.
+ * The buffers stay the CALLER's and must stay unchanged while registered; gt = NULL (or depth / weight = NULL) clears
+ * the registration.  st3r_gs_raster_train ignores it; with a communicator attached the training calls return
+ * ST3R_ERR_INVALID while a prior applies. */
+int st3r_ctx_set_depth_prior(st3r_ctx* ctx, const float* gt, const float* depth, const float* weight, int C, int height,
+                             int width, float depth_fac);
+
 /* fused Adam over the 23 active scalars per gaussian (replaces the 6 torch.optim.Adam of
  * starster/gs.py:37,159-161; sh0 and SH rows 4..23 never receive gradient and are
  * left untouched, their Adam update is exactly 0).  `step` is 1-based. */

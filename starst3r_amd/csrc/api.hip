@@ -221,6 +221,20 @@ int st3r_project_sh_bwd_impl(hipStream_t s, int N, int C, const float* means, co
 int st3r_loss_impl(st3r_ctx* ctx, hipStream_t s, int C, int H, int W, const float* render, const float* gt,
                    float w_l1, float w_ssim, double* sums, float* v_render, bool sums_cleared);
 int st3r_gather_vtile_impl(hipStream_t s, int64_t n_pairs, const st3r_vtile_ref* slots, float* v_splats);
+// the depth prior inside the fused step (gs_blend_depth.hip, loss_depth.hip)
+int st3r_blend_depth_fwd_impl(st3r_ctx* ctx, hipStream_t s, int C, int W, int H, int tile_w, int tile_h,
+                              const float* splats, const int32_t* offsets, const int32_t* flat, int64_t n_isects,
+                              const int32_t* last_ids, float* depth, bool end_in_offsets);
+int st3r_blend_depth_bwd_impl(st3r_ctx* ctx, hipStream_t s, int C, int W, int H, int tile_w, int tile_h,
+                              const float* splats, const int32_t* offsets, const int32_t* flat, int64_t n_isects,
+                              const float* alpha, const int32_t* last_ids, const float* v_depth, const int32_t* cum,
+                              int64_t n_pairs, float* v_splats, bool end_in_offsets, const uint64_t* rectbase, int tight);
+int st3r_add_pairs_impl(hipStream_t s, int64_t n_pairs, float* a, const float* b);
+int st3r_depth_prior_for(st3r_ctx* ctx, hipStream_t s, const float* gt, int C, int H, int W, const float** prior,
+                         const float** weight, const double** norm, float* depth_fac);
+int st3r_depth_prior_loss_impl(st3r_ctx* ctx, hipStream_t s, int C, int H, int W, const float* depth, const float* alpha,
+                               const float* prior, const float* weight, const double* norm, int norm_stride,
+                               float depth_fac, double* sums, int sums_stride, float* v_depth, float* v_alpha);
 
 static int bit_length_u32(uint32_t v) { int n = 0; while (v) { ++n; v >>= 1; } return n; }
 
@@ -441,11 +455,14 @@ static int rasterize_front(st3r_ctx* ctx, hipStream_t s, int N, int C, const flo
 
 __global__ void k_finalize_loss(int C, const double* __restrict__ sums, const double* __restrict__ reg_sums,
                                 double inv_px, double inv_cnt, double w_l1, double w_ssim, double reg_views,
-                                double opac_k, double scale_k, float* __restrict__ loss_out) {
+                                double opac_k, double scale_k, float* __restrict__ loss_out,
+                                const double* __restrict__ dsums, const double* __restrict__ dnorm, double depth_fac) {
     if (threadIdx.x == 0 && blockIdx.x == 0) {
         double loss = 0;
         for (int c = 0; c < C; ++c) loss += w_l1 * sums[2 * c] * inv_px + w_ssim * (1.0 - sums[2 * c + 1] * inv_cnt);
         loss += reg_views * (opac_k * reg_sums[0] + scale_k * reg_sums[1]);
+        if (dsums)   // depth prior (loss_depth.hip): depth_fac sum_p w |ED - Z| / n_c per view
+            for (int c = 0; c < C; ++c) loss += depth_fac * dsums[c] / dnorm[c];
         loss_out[0] = (float)loss;
     }
 }
@@ -461,8 +478,21 @@ static int train_views(st3r_ctx* ctx, hipStream_t s, int N, int C, const float* 
                        const float* scales, const float* opacities, const float* sh, int sh_stride,
                        const float* viewmats, const float* Ks, const float* campos, const float* gt_images, int W, int H,
                        float ssim_fac, float opac_fac, float scale_fac, double* sums, double* reg_sums, bool allow_async,
-                       bool accumulate, float* grads, RasterOut* ro_out, float* v_viewmats = nullptr) {
+                       bool accumulate, float* grads, RasterOut* ro_out, float* v_viewmats = nullptr,
+                       double* dp_sums = nullptr) {
+    // dp_sums != NULL: a depth prior is registered for these views (st3r_ctx_set_depth_prior) -- the step also renders the
+    // depth map of the same lists, takes the prior's loss (sum_p w |ED - Z| per view -> dp_sums) and sends v_D and v_alpha
+    // back: the colour backward receives v_alpha, the depth backward writes slots of its own, both per-pair arrays are
+    // materialised by the stand-alone gathers (k_gather_vtile, k_gather_vtile_depth), added, and the projection backward
+    // reads the sum as st3r_gs_project_sh_bwd does; st3r_gs_depth_bwd then adds the float-9 column.  The kernels and the
+    // order of the unfused chain (render_3dgs "RGB+ED" through autograd).
     const int64_t n_pairs = (int64_t)N * C, n_px = (int64_t)C * H * W;
+    const float* dp_prior = nullptr; const float* dp_weight = nullptr; const double* dp_norm = nullptr; float dp_fac = 0.f;
+    if (dp_sums) {
+        int rc_ = st3r_depth_prior_for(ctx, s, gt_images, C, H, W, &dp_prior, &dp_weight, &dp_norm, &dp_fac);
+        if (rc_) return rc_;
+    }
+    const bool dp = dp_prior != nullptr;
     RasterOut ro;
     int rc = rasterize_front(ctx, s, N, C, means, quats, scales, opacities, sh, sh_stride, viewmats, Ks, campos, W, H,
                              reg_sums, 1, nullptr, allow_async, &ro, sums);
@@ -475,22 +505,48 @@ static int train_views(st3r_ctx* ctx, hipStream_t s, int N, int C, const float* 
     // Round 5: the per-pair sums of the backward's (record, tile) slots are taken inside the projection backward: no
     // 48-byte per-pair gradient records, no k_gather_vtile launch (that kernel serves the stand-alone st3r_gs_blend_bwd and
     // st3r_gs_raster_train)
-    float* const v_splats = nullptr;
-    st3r_vtile_ref slots_{}; st3r_vtile_ref* const slots = &slots_;
+    float* v_splats = nullptr;
+    st3r_vtile_ref slots_{}; const st3r_vtile_ref* slots = &slots_;
+    float* depth = nullptr; float* v_depth = nullptr; float* v_alpha = nullptr;
+    if (dp) {
+        GET(SLOT_DEPTH, float, n_px, depth_);
+        GET(SLOT_VDEPTH, float, n_px, v_depth_);
+        GET(SLOT_VALPHA, float, n_px, v_alpha_);
+        depth = depth_; v_depth = v_depth_; v_alpha = v_alpha_;
+    }
     st3r_prof_begin(ctx, s, STG_BLEND_FWD);
     rc = st3r_blend_fwd_impl(ctx, s, C, W, H, ro.tile_w, ro.tile_h, ro.splats, ro.offsets, ro.flat, ro.n_isects, rgb,
                              alpha, last, true, eio);
+    if (!rc && dp)
+        rc = st3r_blend_depth_fwd_impl(ctx, s, C, W, H, ro.tile_w, ro.tile_h, ro.splats, ro.offsets, ro.flat, ro.n_isects,
+                                       last, depth, eio);
     st3r_prof_end(ctx, s, STG_BLEND_FWD);
     if (rc) return rc;
     st3r_prof_begin(ctx, s, STG_LOSS);
     rc = st3r_loss_impl(ctx, s, C, H, W, rgb, gt_images, 1.0f - ssim_fac, ssim_fac, sums, v_rgb, true);
+    if (!rc && dp)
+        rc = st3r_depth_prior_loss_impl(ctx, s, C, H, W, depth, alpha, dp_prior, dp_weight, dp_norm, 1, dp_fac, dp_sums, 1,
+                                        v_depth, v_alpha);
     st3r_prof_end(ctx, s, STG_LOSS);
     if (rc) return rc;
     st3r_prof_begin(ctx, s, STG_BLEND_BWD);
     rc = st3r_blend_bwd_impl(ctx, s, C, W, H, ro.tile_w, ro.tile_h, ro.splats, ro.offsets, ro.flat, ro.n_isects, alpha,
-                             last, v_rgb, nullptr, ro.cum, (ctx->debug_flags & 2) ? nullptr : ro.rects,
-                             (ctx->debug_flags & 2) ? nullptr : ro.rectbase, 1, n_pairs, v_splats,
-                             eio, slots);
+                             last, v_rgb, v_alpha, ro.cum, (ctx->debug_flags & 2) ? nullptr : ro.rects,
+                             (ctx->debug_flags & 2) ? nullptr : ro.rectbase, 1, n_pairs, nullptr,
+                             eio, &slots_);
+    if (!rc && dp) {
+        GET(SLOT_VSPLATS, float, n_pairs * ST3R_SPLAT_STRIDE, v_pairs);
+        GET(SLOT_VSPLATS_D, float, n_pairs * ST3R_SPLAT_STRIDE, v_pairs_d);
+        rc = st3r_blend_depth_bwd_impl(ctx, s, C, W, H, ro.tile_w, ro.tile_h, ro.splats, ro.offsets, ro.flat, ro.n_isects,
+                                       alpha, last, v_depth, ro.cum, n_pairs, v_pairs_d, eio,
+                                       (ctx->debug_flags & 2) ? nullptr : ro.rectbase, 1);
+        if (!rc) {
+            if (slots_.vtile) rc = st3r_gather_vtile_impl(s, n_pairs, &slots_, v_pairs);
+            else HIP_TRY(hipMemsetAsync(v_pairs, 0, sizeof(float) * ST3R_SPLAT_STRIDE * (size_t)n_pairs, s));   // no records
+        }
+        if (!rc) rc = st3r_add_pairs_impl(s, n_pairs, v_pairs, v_pairs_d);
+        v_splats = v_pairs; slots = nullptr;   // the projection backward reads the per-pair sums
+    }
     st3r_prof_end(ctx, s, STG_BLEND_BWD);
     if (rc) return rc;
     st3r_prof_begin(ctx, s, STG_PROJECT_BWD);
@@ -520,8 +576,18 @@ static int train_views(st3r_ctx* ctx, hipStream_t s, int N, int C, const float* 
                                       0.3f, ro.splats, v_splats, (float)C, opac_fac, scale_fac, grads, accumulate, 0, -1,
                                       false, slots);
     }
-    st3r_prof_end(ctx, s, STG_PROJECT_BWD);
     *ro_out = ro;
+    if (dp) {
+        // the pose gradient of the summed per-pair gradients first, then the float-9 column into the means block and into
+        // row 2 of v_viewmats: the order of _RasterizeDepth.backward
+        if (!rc && v_viewmats)
+            rc = st3r_gs_viewmat_bwd(ctx, s, N, C, means, quats, scales, sh, sh_stride, viewmats, Ks, campos, W, H, 0.3f,
+                                     ro.splats, v_splats, v_viewmats);
+        if (!rc) rc = st3r_gs_depth_bwd(ctx, s, N, C, means, viewmats, ro.splats, v_splats, grads, v_viewmats);
+        st3r_prof_end(ctx, s, STG_PROJECT_BWD);
+        return rc;
+    }
+    st3r_prof_end(ctx, s, STG_PROJECT_BWD);
     if (!rc && v_viewmats) {
         GET(SLOT_VSPLATS, float, n_pairs * ST3R_SPLAT_STRIDE, v_pairs);
         rc = st3r_gather_vtile_impl(s, n_pairs, slots, v_pairs);
@@ -548,6 +614,22 @@ int st3r_train_fwd_bwd_impl(st3r_ctx* ctx, void* stream, int N, int C, const flo
     double* sums = small;              // [C,2]
     double* reg_sums = small + 2 * C;  // [4]: sum sigmoid(o), sum exp(s), visible pairs, reference intersections
     double* reg_scratch = reg_sums + 4;   // the same of the later view chunks (their regulariser sums are repeats)
+    // a depth prior registered for these views (st3r_ctx_set_depth_prior): its per-view sums, and whether it applies at all
+    double* dp_sums = nullptr; const double* dp_norm = nullptr; float dp_fac = 0.f;
+    {
+        const float* zp; const float* wp;
+        int rc_ = st3r_depth_prior_for(ctx, s, gt_images, C, H, W, &zp, &wp, &dp_norm, &dp_fac);
+        if (rc_) return rc_;
+        if (zp) {
+            if (ctx->comm) {
+                st3r_set_error("a depth prior is registered and a communicator is attached -- the depth term is not "
+                               "supported in view-sharded training (clear it with st3r_ctx_set_depth_prior(ctx, NULL, ...))");
+                return ST3R_ERR_INVALID;
+            }
+            GET(SLOT_DPRIOR_SUMS, double, (size_t)C, ds);
+            dp_sums = ds;
+        }
+    }
     st3r_prof_next_step(ctx);
     int rc = settle_pending_count(ctx);
     if (rc) return rc;
@@ -573,7 +655,7 @@ int st3r_train_fwd_bwd_impl(st3r_ctx* ctx, void* stream, int N, int C, const flo
             rc = train_views(ctx, s, N, c1 - c0, means, quats, scales, opacities, sh, sh_stride, viewmats + 16 * c0,
                              Ks + 9 * c0, campos + 3 * c0, gt_images + (int64_t)c0 * H * W * 3, W, H, ssim_fac, opac_fac,
                              scale_fac, sums + 2 * c0, rs, stats_host == nullptr && chunks == 1 && !ctx->comm, !first, grads,
-                             &ro, v_viewmats ? v_viewmats + 16 * c0 : nullptr);
+                             &ro, v_viewmats ? v_viewmats + 16 * c0 : nullptr, dp_sums ? dp_sums + c0 : nullptr);
             if (!rc) { st_vis += ro.n_visible; st_is += ro.n_records; st_ref += ro.n_isects_ref; }
             first = false;
         }
@@ -591,7 +673,7 @@ int st3r_train_fwd_bwd_impl(st3r_ctx* ctx, void* stream, int N, int C, const flo
     const double cnt = (Hi > 0 && Wi > 0) ? (double)Hi * Wi * 3 : 0.0;
     hipLaunchKernelGGL(k_finalize_loss, dim3(1), dim3(64), 0, s, C, sums, reg_sums, 1.0 / ((double)H * W * 3),
                        cnt > 0 ? 1.0 / cnt : 0.0, (double)(1.0f - ssim_fac), (double)ssim_fac, (double)C,
-                       (double)opac_fac / N, (double)scale_fac / (3.0 * N), loss_out);
+                       (double)opac_fac / N, (double)scale_fac / (3.0 * N), loss_out, dp_sums, dp_norm, (double)dp_fac);
     LAUNCH_CHECK();
     if (stats_host) {
         stats_host[0] = st_vis; stats_host[1] = st_is; stats_host[2] = st3r_ctx_arena_bytes(ctx);
@@ -655,7 +737,8 @@ ST3R_EXPORT int st3r_gs_raster_train(st3r_ctx* ctx, void* stream, int N, int C, 
     const int Hi = H - 10, Wi = W - 10;
     const double cnt = (Hi > 0 && Wi > 0) ? (double)Hi * Wi * 3 : 0.0;
     hipLaunchKernelGGL(k_finalize_loss, dim3(1), dim3(64), 0, s, C, sums, reg_sums, 1.0 / ((double)H * W * 3),
-                       cnt > 0 ? 1.0 / cnt : 0.0, (double)(1.0f - ssim_fac), (double)ssim_fac, 0.0, 0.0, 0.0, loss_out);
+                       cnt > 0 ? 1.0 / cnt : 0.0, (double)(1.0f - ssim_fac), (double)ssim_fac, 0.0, 0.0, 0.0, loss_out,
+                       (const double*)nullptr, (const double*)nullptr, 0.0);
     LAUNCH_CHECK();
     if (stats_host) {
         stats_host[0] = -1; stats_host[1] = ro.n_records; stats_host[2] = st3r_ctx_arena_bytes(ctx); stats_host[3] = -1;

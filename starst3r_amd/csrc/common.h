@@ -79,6 +79,13 @@ enum ArenaSlot {
     SLOT_VTILE_DEPTH, // depth blend backward (gs_blend_depth.hip): its own stamped per-(record, tile) slots, 32 bytes each
     SLOT_DEPTH_PART,  // depth -> poses (gs_blend_depth.hip): one 4-double partial per (camera, block of 256 Gaussians)
     SLOT_POSE_GRAD,   // fused step with poses (gs_pose_step.hip): v_viewmats [C,4,4] of the step when the caller wants no copy
+    SLOT_DEPTH,       // fused step with a depth prior (api.hip): the accumulated depth D [C,H,W] of the step's render
+    SLOT_VDEPTH,      // the same: d loss / d D [C,H,W]
+    SLOT_VALPHA,      // the same: d loss / d alpha [C,H,W] (the derivative through ED = D / alpha)
+    SLOT_VSPLATS_D,   // the same: the per-pair gradients of the depth blend backward, added to SLOT_VSPLATS
+    SLOT_DPRIOR_PART, // depth-prior loss (loss_depth.hip): one double partial per (view, workgroup)
+    SLOT_DPRIOR_NORM, // the same: n_c = max(sum w_c, 1) of every registered view, computed once per registration
+    SLOT_DPRIOR_SUMS, // the same: sum_p w |ED - Z| per view of the fused step
     SLOT_COUNT
 };
 
@@ -122,6 +129,9 @@ struct st3r_ctx {
                       // in a kernel of their own -- left the library in round 6: tools/experiments/README.md)
     // ground-truth moments registered by the caller (st3r_ctx_set_gt_moments, loss.hip): caller-owned, valid until cleared
     const float* gtm_gt; const float* gtm_mom; int gtm_c, gtm_h, gtm_w;
+    // depth prior registered by the caller (st3r_ctx_set_depth_prior, loss_depth.hip): caller-owned, valid until cleared;
+    // dp_norm_valid: SLOT_DPRIOR_NORM holds the n_c of this registration (computed by the first training call that uses it)
+    const float* dp_gt; const float* dp_depth; const float* dp_weight; int dp_c, dp_h, dp_w; float dp_fac; int dp_norm_valid;
     int bwd_stamp;  // generation stamp of the per-(record, tile) partial-gradient slots
     int depth_stamp;  // the same for the depth backward's slots (SLOT_VTILE_DEPTH)
     uint32_t scan_gen;   // single-pass scan (gs_isect.hip): generation of its status words

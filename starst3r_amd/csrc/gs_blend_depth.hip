@@ -54,7 +54,8 @@ __device__ __forceinline__ DepthTile depth_tile_geom(int C, int W, int H, int ti
     g.inside = (g.i < H) && (g.j < W);
     g.px = (float)g.j + 0.5f; g.py = (float)g.i + 0.5f;
     g.start = offsets[g.lb];
-    g.end = (g.lb == total - 1) ? n_isects : offsets[g.lb + 1];
+    // n_isects < 0 (fused step): the table carries the record total as its last entry, as for the colour kernels
+    g.end = (n_isects >= 0 && g.lb == total - 1) ? n_isects : offsets[g.lb + 1];
     return g;
 }
 
@@ -145,6 +146,18 @@ static int forward_hand_off(st3r_ctx* ctx, int C, int tile_w, int tile_h, int64_
     return ST3R_OK;
 }
 
+// end_in_offsets (fused step): offsets has C * tiles + 1 entries and the last one closes the last tile -- the record
+// count may then live on the device, n_isects being a capacity
+int st3r_blend_depth_fwd_impl(st3r_ctx* ctx, hipStream_t s, int C, int W, int H, int tile_w, int tile_h,
+                              const float* splats, const int32_t* offsets, const int32_t* flat, int64_t n_isects,
+                              const int32_t* last_ids, float* depth, bool end_in_offsets) {
+    (void)ctx;
+    hipLaunchKernelGGL(k_blend_depth_fwd, dim3(C * tile_w * tile_h), dim3(BLK), 0, s, C, W, H, tile_w, tile_h,
+                       (const float4*)splats, offsets, flat, end_in_offsets ? -1 : (int)n_isects, last_ids, depth);
+    LAUNCH_CHECK();
+    return ST3R_OK;
+}
+
 ST3R_EXPORT int st3r_gs_blend_depth_fwd(st3r_ctx* ctx, void* stream, int C, int width, int height, int tile_size,
                                         int tile_w, int tile_h, const float* splats, const int32_t* offsets,
                                         const int32_t* flatten_ids, int64_t n_isects, const float* alpha,
@@ -154,10 +167,8 @@ ST3R_EXPORT int st3r_gs_blend_depth_fwd(st3r_ctx* ctx, void* stream, int C, int 
     ARG_CHECK(splats && offsets && alpha && last_ids && depth && n_isects >= 0 && n_isects < 2147483647LL);
     ARG_CHECK(n_isects == 0 || flatten_ids);
     (void)alpha;   // (part of the colour render's result the call is bound to; T is rebuilt from the records)
-    hipLaunchKernelGGL(k_blend_depth_fwd, dim3(C * tile_w * tile_h), dim3(BLK), 0, (hipStream_t)stream, C, width, height,
-                       tile_w, tile_h, (const float4*)splats, offsets, flatten_ids, (int)n_isects, last_ids, depth);
-    LAUNCH_CHECK();
-    return ST3R_OK;
+    return st3r_blend_depth_fwd_impl(ctx, (hipStream_t)stream, C, width, height, tile_w, tile_h, splats, offsets,
+                                     flatten_ids, n_isects, last_ids, depth, false);
 }
 
 // ------------------------------------------------------------------------------------
@@ -206,7 +217,7 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(8))) void k
     const int32_t* __restrict__ flat, int n_isects, const float* __restrict__ out_alpha,
     const int32_t* __restrict__ last_ids, const float* __restrict__ v_depth, const uint64_t* __restrict__ cmask,
     int64_t cmask_words, const int32_t* __restrict__ tile_nb, const int32_t* __restrict__ cum,
-    float* __restrict__ vtile, int stamp, unsigned vt_cap) {
+    const uint64_t* __restrict__ rectbase, int tight, float* __restrict__ vtile, int stamp, unsigned vt_cap) {
     __shared__ float4 sA[HB];   // x y opacity qa
     __shared__ float4 sB[HB];   // qb qc z -
     __shared__ float sAccW[4][HB * DACC_VALS];            // per wave: the sums of the records it met this round
@@ -276,9 +287,18 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(8))) void k
             if (t == 0) sClampW = cw;
             if (my_cb) {
                 // slot = cum_excl[pid] + index of this tile inside the record's tile rectangle (the emit kernel's integers)
-                const TileRect tr = ref_tile_rect(a.x, a.y, (float)__float_as_int(c.z), 16, tile_w, tile_h);
-                const int cum_excl = my_id == 0 ? 0 : cum[my_id - 1];
-                my_u = cum_excl + ((g.ty0 >> 4) - tr.y0) * (tr.x1 - tr.x0) + ((g.tx0 >> 4) - tr.x0);
+                // (fused step: `cum` scans the TIGHT rectangles the emission used -- slot base and rectangle arrive in one
+                // word per pair, or the rectangle is rebuilt as k_blend_bwd rebuilds it)
+                if (rectbase) {
+                    const uint64_t r = rectbase[my_id];
+                    const int x0 = (int)(r & 0x3FF), y0 = (int)((r >> 10) & 0x3FF), rw = (int)((r >> 20) & 0x3FF);
+                    my_u = (int)(r >> 32) + ((g.ty0 >> 4) - y0) * rw + ((g.tx0 >> 4) - x0);
+                } else {
+                    TileRect tr = ref_tile_rect(a.x, a.y, (float)__float_as_int(c.z), 16, tile_w, tile_h);
+                    if (tight) tr = tight_tile_rect(tr, a.x, a.y, a.z, a.w, b.x, b.y);
+                    const int cum_excl = my_id == 0 ? 0 : cum[my_id - 1];
+                    my_u = cum_excl + ((g.ty0 >> 4) - tr.y0) * (tr.x1 - tr.x0) + ((g.tx0 >> 4) - tr.x0);
+                }
                 my_op = a.z; my_ca = a.w; my_cbb = b.x; my_cc = b.y;
             }
         }
@@ -411,16 +431,11 @@ __global__ __launch_bounds__(256) void k_gather_vtile_depth(int64_t n_pairs, con
     }
 }
 
-ST3R_EXPORT int st3r_gs_blend_depth_bwd(st3r_ctx* ctx, void* stream, int C, int width, int height, int tile_size,
-                                        int tile_w, int tile_h, const float* splats, const int32_t* offsets,
-                                        const int32_t* flatten_ids, int64_t n_isects, const float* alpha,
-                                        const int32_t* last_ids, const float* v_depth, const int32_t* cum_tiles,
-                                        int64_t n_pairs, float* v_splats) {
-    ARG_CHECK(ctx && C > 0 && width > 0 && height > 0 && tile_size == 16);
-    ARG_CHECK(tile_w == (width + 15) / 16 && tile_h == (height + 15) / 16);
-    ARG_CHECK(splats && offsets && alpha && last_ids && v_depth && v_splats && cum_tiles && n_pairs >= 0);
-    ARG_CHECK(n_isects >= 0 && n_isects < 2147483647LL && (n_isects == 0 || flatten_ids));
-    hipStream_t s = (hipStream_t)stream;
+int st3r_blend_depth_bwd_impl(st3r_ctx* ctx, hipStream_t s, int C, int W, int H, int tile_w, int tile_h,
+                              const float* splats, const int32_t* offsets, const int32_t* flat, int64_t n_isects,
+                              const float* alpha, const int32_t* last_ids, const float* v_depth, const int32_t* cum,
+                              int64_t n_pairs, float* v_splats, bool end_in_offsets, const uint64_t* rectbase, int tight) {
+    // rectbase / tight (fused step): `cum` belongs to the tight rectangles of the fused emission (see k_blend_bwd)
     if (n_isects == 0) {
         HIP_TRY(hipMemsetAsync(v_splats, 0, sizeof(float) * ST3R_SPLAT_STRIDE * (size_t)n_pairs, s));
         return ST3R_OK;
@@ -439,12 +454,47 @@ ST3R_EXPORT int st3r_gs_blend_depth_bwd(st3r_ctx* ctx, void* stream, int C, int 
     }
     const int stamp = ++ctx->depth_stamp;
     const unsigned vt_cap = (unsigned)(ctx->slot_bytes[SLOT_VTILE_DEPTH] / (sizeof(float) * DVT_STRIDE));
-    hipLaunchKernelGGL(k_blend_depth_bwd, dim3(C * tile_w * tile_h), dim3(BLK), 0, s, C, width, height, tile_w, tile_h,
-                       (const float4*)splats, offsets, flatten_ids, (int)n_isects, alpha, last_ids, v_depth, cmask, words,
-                       tile_nb, cum_tiles, (float*)p, stamp, vt_cap);
+    hipLaunchKernelGGL(k_blend_depth_bwd, dim3(C * tile_w * tile_h), dim3(BLK), 0, s, C, W, H, tile_w, tile_h,
+                       (const float4*)splats, offsets, flat, end_in_offsets ? -1 : (int)n_isects, alpha, last_ids, v_depth,
+                       cmask, words, tile_nb, cum, rectbase, tight, (float*)p, stamp, vt_cap);
     LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_gather_vtile_depth, dim3(ceil_div(n_pairs, 256)), dim3(256), 0, s, n_pairs, cum_tiles,
+    hipLaunchKernelGGL(k_gather_vtile_depth, dim3(ceil_div(n_pairs, 256)), dim3(256), 0, s, n_pairs, cum,
                        (const float*)p, stamp, vt_cap, (float4*)v_splats);
+    LAUNCH_CHECK();
+    return ST3R_OK;
+}
+
+ST3R_EXPORT int st3r_gs_blend_depth_bwd(st3r_ctx* ctx, void* stream, int C, int width, int height, int tile_size,
+                                        int tile_w, int tile_h, const float* splats, const int32_t* offsets,
+                                        const int32_t* flatten_ids, int64_t n_isects, const float* alpha,
+                                        const int32_t* last_ids, const float* v_depth, const int32_t* cum_tiles,
+                                        int64_t n_pairs, float* v_splats) {
+    ARG_CHECK(ctx && C > 0 && width > 0 && height > 0 && tile_size == 16);
+    ARG_CHECK(tile_w == (width + 15) / 16 && tile_h == (height + 15) / 16);
+    ARG_CHECK(splats && offsets && alpha && last_ids && v_depth && v_splats && cum_tiles && n_pairs >= 0);
+    ARG_CHECK(n_isects >= 0 && n_isects < 2147483647LL && (n_isects == 0 || flatten_ids));
+    return st3r_blend_depth_bwd_impl(ctx, (hipStream_t)stream, C, width, height, tile_w, tile_h, splats, offsets,
+                                     flatten_ids, n_isects, alpha, last_ids, v_depth, cum_tiles, n_pairs, v_splats, false,
+                                     nullptr, 0);
+}
+
+// a += b over the per-pair gradient records (the colour backward's and the depth backward's: float addition, the bits
+// of torch's a.add_(b))
+__global__ __launch_bounds__(256) void k_add_pairs(int64_t n4, float4* __restrict__ a, const float4* __restrict__ b) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+        float4 x = a[i];
+        const float4 y = b[i];
+        x.x += y.x; x.y += y.y; x.z += y.z; x.w += y.w;
+        a[i] = x;
+    }
+}
+
+int st3r_add_pairs_impl(hipStream_t s, int64_t n_pairs, float* a, const float* b) {
+    const int64_t n4 = n_pairs * (ST3R_SPLAT_STRIDE / 4);
+    if (n4 <= 0) return ST3R_OK;
+    int blocks = ceil_div(n4, 256);
+    if (blocks > 256 * 8) blocks = 256 * 8;
+    hipLaunchKernelGGL(k_add_pairs, dim3(blocks), dim3(256), 0, s, n4, (float4*)a, (const float4*)b);
     LAUNCH_CHECK();
     return ST3R_OK;
 }

@@ -327,6 +327,34 @@ def _gt_moments(scene, ctx, gt):
     return scene._gt_mom[1]
 
 
+def _depth_prior_on_device(scene, views, conf_thres, height, width):
+    """scene.depth_maps and the 0/1 weights (depth_confs > conf_thres; all ones without confidences) of `views`, uploaded
+    once and cached like the ground truth (keyed by the tensors and their versions; a numpy map edited in place is not
+    noticed: assign a new one).  Raises ValueError on missing or mis-shaped maps."""
+    maps, confs = getattr(scene, "depth_maps", None) or [], getattr(scene, "depth_confs", None) or []
+    if len(maps) != len(scene.imgs):
+        raise ValueError(f"depth_fac != 0 needs one depth map per image in scene.depth_maps: {len(maps)} maps, "
+                         f"{len(scene.imgs)} images")
+    if confs and len(confs) != len(scene.imgs):
+        raise ValueError(f"scene.depth_confs holds {len(confs)} maps for {len(scene.imgs)} images")
+    for name, lst in (("depth_maps", maps), ("depth_confs", confs)):
+        for i in (views if lst else ()):
+            if tuple(lst[i].shape) != (height, width):
+                raise ValueError(f"scene.{name}[{i}] has shape {tuple(lst[i].shape)}, its image ({height}, {width})")
+    stamp = lambda t: (id(t), getattr(t, "_version", None))   # a map edited in place is uploaded again
+    key = (tuple(views), tuple(stamp(maps[i]) for i in views), tuple(stamp(confs[i]) for i in views) if confs else None,
+           float(conf_thres))
+    if getattr(scene, "_depth_dev", None) is None or scene._depth_dev[0] != key:
+        z = torch.stack([torch.as_tensor(maps[i], dtype=torch.float32) for i in views]).to(scene.device).contiguous()
+        if confs:
+            w = torch.stack([torch.as_tensor(confs[i], dtype=torch.float32) for i in views]).to(scene.device)
+            w = (w > conf_thres).to(torch.float32).contiguous()
+        else:
+            w = torch.ones_like(z)
+        scene._depth_dev = (key, z, w, [maps[i] for i in views], [confs[i] for i in views] if confs else None)
+    return scene._depth_dev[1], scene._depth_dev[2]
+
+
 def run_3dgs_optim(
         scene,
         iters: int,
@@ -337,6 +365,8 @@ def run_3dgs_optim(
         verbose: bool = False,
         pose_lr=0.0,
         pose_freeze=(),
+        depth_fac=0.0,
+        depth_conf_thres=1.5,
     ) -> list:
     """Run 3DGS optimization and pruning (optional) for a number of iterations (reference gs.py:97-166).
 
@@ -352,8 +382,18 @@ def run_3dgs_optim(
     it ends scene.c2w is REPLACED by a new tensor, the inverse of the refined matrices (frozen views keep their rows bit
     for bit).  The pose moments and step counter persist on scene._gs_optim like the Gaussians'.  Single process,
     Gaussians replicated only.
+
+    depth_fac (not in the reference): when not 0.0 the loss of every view gains a depth term inside the same fused step,
+    depth_fac * sum_p w |ED - Z| / max(sum_p w, 1): ED the expected depth of the render (render_mode "ED"), Z the view's
+    map in scene.depth_maps (Scene.add_images keeps the alignment's; they are in the gauge of the poses, so nothing is
+    fitted) and w = 1 where scene.depth_confs exceeds depth_conf_thres, else 0 (all ones when depth_confs is empty).  Works
+    together with pose_lr and enable_pruning; single process, Gaussians replicated only.
     """
     poses_on = callable(pose_lr) or float(pose_lr) != 0.0
+    depth_on = float(depth_fac) != 0.0
+    if depth_on and (_dist.rank_world()[1] > 1 or _sharded_layout(scene, 1, enable_pruning)):
+        raise NotImplementedError("depth_fac != 0 is supported in a single process with replicated Gaussians only "
+                                  "(not under torch.distributed, not with ST3R_MULTI_GPU=gaussian-sharded)")
     if poses_on and (_dist.rank_world()[1] > 1 or _sharded_layout(scene, 1, enable_pruning)):
         raise NotImplementedError("pose_lr != 0 is supported in a single process with replicated Gaussians only "
                                   "(not under torch.distributed, not with ST3R_MULTI_GPU=gaussian-sharded)")
@@ -370,6 +410,8 @@ def run_3dgs_optim(
     w2c = w2c_all[views].contiguous()
     Ks = scene.intrinsics.to(scene.device, torch.float32)[views].contiguous()
     campos = ops.camera_positions(w2c)
+    if depth_on:   # (checked before anything runs)
+        prior, prior_w = _depth_prior_on_device(scene, views, depth_conf_thres, height, width)
     gt = _gt_on_device(scene, views)
     losses = torch.zeros(max(iters, 1), device=scene.device)
     fused = world == 1 or getattr(ctx, "native_comm", False)
@@ -444,6 +486,8 @@ def run_3dgs_optim(
     own_strategy = type(scene.strategy) is MCMCStrategy
     ops.set_gt_moments(ctx, gt, _gt_moments(scene, ctx, gt))
     try:
+        if depth_on:   # the prior belongs to this call: cleared below whatever ends the loop
+            ops.set_depth_prior(ctx, gt, prior, prior_w, float(depth_fac))
         step = 0
         for _ in it_range:
             if enable_pruning:
@@ -490,6 +534,8 @@ def run_3dgs_optim(
                 one_iteration(iters - 1)   # its update was skipped on the device: repeat it
     finally:
         ops.set_gt_moments(ctx, None, None)
+        if depth_on:
+            ops.set_depth_prior(ctx, None, None, None)
         if sh_c[0].shape[0] == g["shN"].shape[0]:
             sh_write_back()
         if restore_exchange is not None:   # (the moments stay complete on every rank: rs_ag goes on using its own piece)

@@ -282,6 +282,34 @@ def set_gt_moments(ctx, gt, moments):
     ctx._gtm_keep = (gt, moments)
 
 
+def loss_depth_prior(ctx, depth, alpha, prior, weight, depth_fac):
+    """Weighted L1 between the expected depth ED = depth / max(alpha, 1e-10) of a render (depth, alpha [C,H,W,1]) and a
+    prior [C,H,W] under weights [C,H,W] >= 0 (st3r_loss_depth_prior).  Returns (sums [C,2] float64: sum_p w |ED - Z| and
+    n_c = max(sum_p w, 1) per view, v_depth, v_alpha [C,H,W,1]); the loss is depth_fac * (sums[:, 0] / sums[:, 1]).sum()."""
+    Cn, H, W = depth.shape[0], depth.shape[1], depth.shape[2]
+    assert alpha.shape == depth.shape and prior.shape == (Cn, H, W) and weight.shape == (Cn, H, W)
+    sums = torch.empty((Cn, 2), dtype=torch.float64, device=depth.device)
+    v_depth, v_alpha = torch.empty_like(depth), torch.empty_like(depth)
+    _lib.check(_lib.lib().st3r_loss_depth_prior(ctx.handle, _stream(), Cn, H, W, _p(depth), _p(alpha), _p(prior),
+                                                _p(weight), depth_fac, _p(sums, torch.float64), _p(v_depth), _p(v_alpha)))
+    return sums, v_depth, v_alpha
+
+
+def set_depth_prior(ctx, gt, depth, weight, depth_fac=1.0):
+    """Register a depth prior (depth, weight [C,H,W]) for the images gt [C,H,W,3] with the ctx -- train_fwd_bwd, train_step
+    and train_step_poses on `gt` (or whole views of it) then add depth_fac * sum_p w |ED - Z| / max(sum_p w, 1) per view to
+    their loss (st3r_ctx_set_depth_prior) -- or clear the registration (gt = None).  The caller's tensors are kept alive
+    here and must stay unchanged while registered."""
+    if gt is None or depth is None or weight is None:
+        _lib.check(_lib.lib().st3r_ctx_set_depth_prior(ctx.handle, None, None, None, 0, 0, 0, 0.0))
+        ctx._dp_keep = None
+        return
+    assert gt.is_contiguous() and depth.shape == tuple(gt.shape[:3]) and weight.shape == tuple(gt.shape[:3])
+    _lib.check(_lib.lib().st3r_ctx_set_depth_prior(ctx.handle, _p(gt), _p(depth), _p(weight), gt.shape[0], gt.shape[1],
+                                                   gt.shape[2], float(depth_fac)))
+    ctx._dp_keep = (gt, depth, weight)
+
+
 def adam_step(ctx, params, grads, m, v, lr, b1, b2, eps, step):
     """params: dict with means, quats, scales, opacities, shN (updated in place)."""
     N = params["means"].shape[0]

@@ -40,7 +40,8 @@ from . import align
 
 class SparseGAResult:
     """The members of Mast3r's SparseGA that the reference touches (scene.py:133,138-139,148):
-    .imgs, .cam2w, .intrinsics, .get_dense_pts3d(clean_depth=True) -> (pts list, depthmaps list, confs list)."""
+    .imgs, .cam2w, .intrinsics, .get_dense_pts3d(clean_depth=True) -> (pts list, depthmaps list, confs list).
+    Not in Mast3r: .get_dense_depth() -> the per-pixel depth maps of the same unprojection."""
 
     def __init__(self, imgs, res, dense=None):
         self.imgs = imgs
@@ -79,7 +80,25 @@ class SparseGAResult:
             conf = ops.dense_clean(ctx, start, sizes, self._res["_cam_rows"], pts, z, conf)
         bounds = start.tolist()
         sl = [slice(bounds[i], bounds[i + 1]) for i in range(len(counts))]
+        self._dense_z = [z[s_] for s_ in sl]   # own-camera depth of every dense pixel (get_dense_depth)
         return [pts[s_] for s_ in sl], list(self.depthmaps), [conf[s_].cpu() for s_ in sl]
+
+    def get_dense_depth(self):
+        """The depth of every dense pixel in its own camera, one [H, W] float32 tensor per view, in the alignment's units
+        -- the gauge of cam2w, intrinsics and the dense points, so a depth term needs no scale or shift.  It is the `z`
+        the last get_dense_pts3d computed (st3r_dense_unproject) and is handed over (not kept); that call is made here if none
+        has been since.  Needs one dense
+        entry per pixel, in raster order."""
+        if getattr(self, "_dense_z", None) is None:
+            self.get_dense_pts3d(clean_depth=False)
+        out = []
+        for im, z in zip(self.imgs, self._dense_z):
+            h, w = np.asarray(im).shape[:2]
+            if z.numel() != h * w:
+                raise ValueError("dense depth maps need one dense entry per pixel, in raster order")
+            out.append(z.reshape(h, w))
+        self._dense_z = None   # handed over: the result does not keep the device copy alive
+        return out
 
 
 def flatten_reference_inputs(imgs, imsizes, pps, base_focals, core_depth, anchors, corres, corres2d, preds_21, mst,

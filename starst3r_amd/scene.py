@@ -24,6 +24,10 @@ class Scene:
         self.imgs = []
         self.dense_pts = []
         self.dense_cols = []
+        # not in the reference: per view the alignment's depth of every pixel in its own camera and the cleaned confidence
+        # that goes with it, both [H, W] -- the prior of run_3dgs_optim(depth_fac=...); a user may assign other maps
+        self.depth_maps = []
+        self.depth_confs = []
         self.c2w = None
         self.intrinsics = None
         self.optim_params = None
@@ -76,6 +80,12 @@ class Scene:
         keep = [(confs[i] > conf_thres).reshape(-1).cpu() for i in range(len(result.imgs))]
         self.dense_pts = [pts[i].cpu()[k] for i, k in enumerate(keep)]
         self.dense_cols = [torch.as_tensor(result.imgs[i]).reshape(-1, 3)[k] for i, k in enumerate(keep)]
+        # the depth maps of the same unprojection (all pixels, not only the confident ones) and their confidences
+        get_depth = getattr(result, "get_dense_depth", None)
+        maps = get_depth() if get_depth is not None else []
+        self.depth_maps = [z.detach().float().cpu() for z in maps]
+        self.depth_confs = [torch.as_tensor(confs[i]).detach().float().cpu().reshape(z.shape)
+                            for i, z in enumerate(self.depth_maps)]
 
     def init_3dgs(self, init_scale=3e-3, lr=1e-3):
         _gs.init_3dgs(self, init_scale, lr)
@@ -91,8 +101,14 @@ class Scene:
         return _gs.render_3dgs_original(self, width, height, render_mode=render_mode)
 
     def run_3dgs_optim(self, iters: int, enable_pruning: bool = False, loss_ssim_fac=0.2, loss_opacity_fac=0.01,
-                       loss_scale_fac=0.01, verbose: bool = False, pose_lr=0.0, pose_freeze=()) -> list:
-        if not callable(pose_lr) and float(pose_lr) == 0.0 and not tuple(pose_freeze):   # the reference's call
+                       loss_scale_fac=0.01, verbose: bool = False, pose_lr=0.0, pose_freeze=(), depth_fac=0.0,
+                       depth_conf_thres=1.5) -> list:
+        poses_off = not callable(pose_lr) and float(pose_lr) == 0.0 and not tuple(pose_freeze)
+        if float(depth_fac) != 0.0:
+            return _gs.run_3dgs_optim(self, iters, enable_pruning, loss_ssim_fac, loss_opacity_fac, loss_scale_fac,
+                                      verbose, pose_lr=pose_lr, pose_freeze=pose_freeze, depth_fac=depth_fac,
+                                      depth_conf_thres=depth_conf_thres)
+        if poses_off:   # the reference's call
             return _gs.run_3dgs_optim(self, iters, enable_pruning, loss_ssim_fac, loss_opacity_fac, loss_scale_fac,
                                       verbose)
         return _gs.run_3dgs_optim(self, iters, enable_pruning, loss_ssim_fac, loss_opacity_fac, loss_scale_fac,
