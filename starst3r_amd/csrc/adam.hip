@@ -7,7 +7,7 @@
 // grads / m / v use the block layout means[3N] quats[4N] scales[3N] opacities[N] sh4[12N];
 // parameters are updated in place in the caller's tensors (sh with row stride sh_stride).
 // Arithmetic mirrors torch.optim.Adam's single-tensor path (see oracle/gs_oracle.c gso_adam).
-#include "common.h"
+#include "stages.h"
 
 struct AdamK {
     float step_size, bc2_sqrt, w1, w2, b2, eps;
@@ -168,7 +168,6 @@ static AdamK adam_constants(double lr, double b1, double b2, double eps, int ste
     return k;
 }
 
-// i0 < 0: the whole buffer.  [g0, g1) a proper sub-range of the Gaussians: that range instead of [i0, i1).
 int st3r_adam_impl(hipStream_t s, int N, float* means, float* quats, float* scales, float* opacities, float* sh,
                    int sh_stride, const float* grads, float* m, float* v, double lr, double b1, double b2,
                    double eps, int step, const int32_t* count_dev, uint32_t count_cap, const int32_t* status_dev, int64_t i0,
@@ -212,7 +211,6 @@ int st3r_params_from_stage_impl(hipStream_t s, int N, float* means, float* quats
     return ST3R_OK;
 }
 
-// the device-side guard of an asynchronous step that is still in flight (see k_adam)
 // (word 0 of the counts buffer: the record count of the step, compared with its capacity.  Word 4 of the same buffer is
 // the status word of an exchanged step; it is NOT part of this guard: st3r_gs_train_step hands it to the kernels itself.)
 void st3r_adam_guard(st3r_ctx* ctx, const int32_t** count_dev, uint32_t* count_cap) {

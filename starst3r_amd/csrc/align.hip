@@ -753,12 +753,8 @@ ST3R_EXPORT int st3r_align_run_opts(st3r_ctx* ctx, void* stream, int C, int G, i
     S.pps = pps; S.log_focals = log_focals; S.quats = quats; S.trans = trans; S.log_sizes = log_sizes;
     S.m = work; S.v = work + 11 * C; S.cam = work + 22 * C; S.acc = S.cam + (int64_t)C * CAM_STRIDE;
     S.losses = losses_out;
-    {   // the chain cache of k_align_update: 12 floats per view
-        void* pc;
-        int rc = st3r_arena_get(ctx, SLOT_ALIGN_CTL, sizeof(float) * (size_t)(12 * C), &pc);
-        if (rc) return rc;
-        S.chain = (float*)pc;
-    }
+    ARENA_GET(SLOT_ALIGN_CTL, float, 12 * C, chain);   // the chain cache of k_align_update: 12 floats per view
+    S.chain = chain;
     auto lr_of = [&](int stage, int it, int li) -> float {
         const int niter = stage == 1 ? niter1 : niter2;
         const float lr_base = stage == 1 ? lr1 : lr2;
@@ -777,12 +773,8 @@ ST3R_EXPORT int st3r_align_run_opts(st3r_ctx* ctx, void* stream, int C, int G, i
     // are added by k_align_update itself, more by k_align_reduce (one thread per accumulator word)
     const int max_rows = (n_corr > n_c2d ? n_corr : n_c2d) + n_dust;
     const int rpt = max_rows > 0 ? ceil_div(ceil_div(max_rows, 256), 1024) : 1;
-    {
-        void* pp;
-        int rc = st3r_arena_get(ctx, SLOT_SCAN_TMP, sizeof(float) * 1024 * ((size_t)C * ACC_STRIDE + 1), &pp);
-        if (rc) return rc;
-        S.part = (float*)pp;
-    }
+    ARENA_GET(SLOT_SCAN_TMP, float, 1024 * ((size_t)C * ACC_STRIDE + 1), part);
+    S.part = part;
     {   // constants of every anchor, packed once so that the residual kernel has a single dependent load level
         void* pk;
         int rc = st3r_arena_get(ctx, SLOT_NN_PART, sizeof(float4) * 2 * (size_t)(n_anchors > 0 ? n_anchors : 1), &pk);

@@ -52,7 +52,7 @@
 #include <chrono>
 #include <thread>
 
-#include "common.h"
+#include "stages.h"
 
 namespace {
 struct RcclApi {
@@ -197,15 +197,6 @@ ST3R_EXPORT int st3r_grad_allreduce(st3r_ctx* ctx, void* stream, float* grads, i
     return ST3R_OK;
 }
 
-int st3r_adam_impl(hipStream_t s, int N, float* means, float* quats, float* scales, float* opacities, float* sh,
-                   int sh_stride, const float* grads, float* m, float* v, double lr, double b1, double b2,
-                   double eps, int step, const int32_t* count_dev, uint32_t count_cap, const int32_t* status_dev, int64_t i0,
-                   int64_t i1, int64_t g0, int64_t g1, float* pstage, const float* gstage, float* grads_out);
-int st3r_params_from_stage_impl(hipStream_t s, int N, float* means, float* quats, float* scales, float* opacities,
-                                float* sh, int sh_stride, const float* pstage, int64_t i0, int64_t i1, int64_t lim,
-                                const int32_t* count_dev, uint32_t count_cap, const int32_t* status_dev);
-void st3r_adam_guard(st3r_ctx* ctx, const int32_t** count_dev, uint32_t* count_cap);
-
 #define EXCH_RANGES_K 4
 
 // Under st3r_gs_train_step with ST3R_EXCHANGE_RS_AG a rank maintains the Adam moments of ITS piece of the 23N buffer
@@ -243,7 +234,6 @@ static int ensure_comm_stream(st3r_ctx* ctx) {
 // ranks the Adam update of the step is skipped on the device (k_adam's guard reads the reduced word), and every other
 // rank learns about it at its next training call (or st3r_ctx_settle): ST3R_ERR_PEER, parameters untouched,
 // replicas still identical.
-int st3r_counts_buffer(st3r_ctx* ctx, hipStream_t s, int32_t** out);   // api.hip: 16 device words, zeroed when allocated
 #define PEER_WORD 4           // index of the status word inside the counts buffer
 #define PEER_PINNED 24        // its read-back slot in ctx->pinned (int64 units)
 
@@ -463,10 +453,6 @@ __global__ __launch_bounds__(256) void k_xreduce(const float* const* __restrict_
         out[i] = acc;
     }
 }
-
-int st3r_params_from_peers_impl(hipStream_t s, int N, float* means, float* quats, float* scales, float* opacities,
-                                float* sh, int sh_stride, const float* const* tab, int r, int64_t q, int64_t lim,
-                                const int32_t* status_dev);
 
 // One whole iteration of starster/gs.py:143-164 for this rank's C views: render -> loss -> backward ->
 // (exchange of the gradients when a communicator is attached: see the head of this file) -> Adam.  Asynchronous apart

@@ -79,7 +79,7 @@ enum ArenaSlot {
     SLOT_VTILE_DEPTH, // depth blend backward (gs_blend_depth.hip): its own stamped per-(record, tile) slots, 32 bytes each
     SLOT_DEPTH_PART,  // depth -> poses (gs_blend_depth.hip): one 4-double partial per (camera, block of 256 Gaussians)
     SLOT_POSE_GRAD,   // fused step with poses (gs_pose_step.hip): v_viewmats [C,4,4] of the step when the caller wants no copy
-    SLOT_DEPTH,       // fused step with a depth prior (api.hip): the accumulated depth D [C,H,W] of the step's render
+    SLOT_DEPTH,       // fused step with a depth prior (fused_step.hip): the accumulated depth D [C,H,W] of the step's render
     SLOT_VDEPTH,      // the same: d loss / d D [C,H,W]
     SLOT_VALPHA,      // the same: d loss / d alpha [C,H,W] (the derivative through ED = D / alpha)
     SLOT_VSPLATS_D,   // the same: the per-pair gradients of the depth blend backward, added to SLOT_VSPLATS
@@ -171,6 +171,16 @@ void st3r_prof_next_step(st3r_ctx* ctx);
 int st3r_arena_get(st3r_ctx* ctx, int slot, size_t bytes, void** out);
 // same, *grown = 1 when the slot was (re)allocated by this call
 int st3r_arena_get2(st3r_ctx* ctx, int slot, size_t bytes, void** out, int* grown);
+// declares `type* var` = the scratch of `slot` with room for `count` elements; on failure the enclosing function (which
+// has a `ctx`) returns the error code
+#define ARENA_GET(slot, type, count, var)                                                    \
+    type* var;                                                                               \
+    {                                                                                        \
+        void* _p;                                                                            \
+        int _rc = st3r_arena_get(ctx, slot, sizeof(type) * (size_t)(count), &_p);            \
+        if (_rc) return _rc;                                                                 \
+        var = (type*)_p;                                                                     \
+    }
 
 static inline int ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 

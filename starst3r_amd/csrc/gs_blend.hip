@@ -51,7 +51,7 @@
 // include/skip decisions.
 #include <type_traits>
 
-#include "common.h"
+#include "stages.h"
 #include "tile_rect.h"
 #include "blend_common.h"
 
@@ -228,27 +228,19 @@ static int hand_off_buffers(st3r_ctx* ctx, int C, int tile_w, int tile_h, int64_
                             int64_t* words, int32_t** tile_nb) {
     const int64_t total = (int64_t)C * tile_w * tile_h;
     *words = (n_isects >> 6) + 4 * total + 8;
-    void* p;
-    int rc = st3r_arena_get(ctx, SLOT_CMASK, sizeof(uint64_t) * 4 * (size_t)*words, &p);
-    if (rc) return rc;
-    *cmask = (uint64_t*)p;
-    rc = st3r_arena_get(ctx, SLOT_TILE_NB, sizeof(int32_t) * (size_t)total, &p);
-    if (rc) return rc;
-    *tile_nb = (int32_t*)p;
+    ARENA_GET(SLOT_CMASK, uint64_t, 4 * (size_t)*words, cm);
+    ARENA_GET(SLOT_TILE_NB, int32_t, total, nb);
+    *cmask = cm; *tile_nb = nb;
     return ST3R_OK;
 }
 
-int st3r_blend_fwd_cells_impl(st3r_ctx* ctx, hipStream_t s, int C, int W, int H, int tile_w, int tile_h,
-                              const float* splats, const int32_t* offsets, const int32_t* flat, float* rgb, float* alpha,
-                              int32_t* last_ids, uint64_t* cmask, int64_t cmask_words, int32_t* tile_nb);
-
-int st3r_blend_fwd_impl(st3r_ctx* ctx, hipStream_t s, int C, int W, int H, int tile_w, int tile_h,
-                        const float* splats, const int32_t* offsets, const int32_t* flat, int64_t n_isects,
-                        float* rgb, float* alpha, int32_t* last_ids, bool for_backward, bool end_in_offsets) {
+int st3r_blend_fwd_impl(st3r_ctx* ctx, hipStream_t s, const RasterOut& ro, float* rgb, float* alpha, int32_t* last_ids,
+                        bool for_backward, bool end_in_offsets) {
+    const int C = ro.C, W = ro.W, H = ro.H, tile_w = ro.tile_w, tile_h = ro.tile_h;
     const int total = C * tile_w * tile_h;
     uint64_t* cmask = nullptr; int64_t words = 0; int32_t* tile_nb = nullptr;
     if (for_backward) {
-        int rc = hand_off_buffers(ctx, C, tile_w, tile_h, n_isects, &cmask, &words, &tile_nb);
+        int rc = hand_off_buffers(ctx, C, tile_w, tile_h, ro.n_isects, &cmask, &words, &tile_nb);
         if (rc) return rc;
     }
     // the fused training calls (their own backward follows) take the TRAIN variant; debug flag 128 keeps them on the
@@ -256,14 +248,13 @@ int st3r_blend_fwd_impl(st3r_ctx* ctx, hipStream_t s, int C, int W, int H, int t
     // the fused training calls blend with cell lists (gs_blend_cells.hip; debug flag 128 keeps them on the quadrant
     // kernel, flag 512 sends st3r_gs_render through the cell kernel as well: A/B and tests)
     if ((for_backward && end_in_offsets && !(ctx->debug_flags & 128)) || (end_in_offsets && (ctx->debug_flags & 512)))
-        return st3r_blend_fwd_cells_impl(ctx, s, C, W, H, tile_w, tile_h, splats, offsets, flat, rgb, alpha, last_ids, cmask,
-                                         words, tile_nb);
+        return st3r_blend_fwd_cells_impl(ctx, s, ro, rgb, alpha, last_ids, cmask, words, tile_nb);
     if (for_backward && end_in_offsets)
-        hipLaunchKernelGGL(k_blend_fwd<true>, dim3(total), dim3(BLK), 0, s, C, W, H, tile_w, tile_h, (const float4*)splats,
-                           offsets, flat, -1, rgb, alpha, last_ids, cmask, words, tile_nb, ctx->debug_flags & 1);
+        hipLaunchKernelGGL(k_blend_fwd<true>, dim3(total), dim3(BLK), 0, s, C, W, H, tile_w, tile_h, (const float4*)ro.splats,
+                           ro.offsets, ro.flat, -1, rgb, alpha, last_ids, cmask, words, tile_nb, ctx->debug_flags & 1);
     else
-        hipLaunchKernelGGL(k_blend_fwd<false>, dim3(total), dim3(BLK), 0, s, C, W, H, tile_w, tile_h, (const float4*)splats,
-                           offsets, flat, end_in_offsets ? -1 : (int)n_isects, rgb, alpha, last_ids, cmask, words, tile_nb,
+        hipLaunchKernelGGL(k_blend_fwd<false>, dim3(total), dim3(BLK), 0, s, C, W, H, tile_w, tile_h, (const float4*)ro.splats,
+                           ro.offsets, ro.flat, end_in_offsets ? -1 : (int)ro.n_isects, rgb, alpha, last_ids, cmask, words, tile_nb,
                            ctx->debug_flags & 1);
     LAUNCH_CHECK();
     return ST3R_OK;
@@ -277,8 +268,9 @@ ST3R_EXPORT int st3r_gs_blend_fwd(st3r_ctx* ctx, void* stream, int C, int width,
     ARG_CHECK(tile_w == (width + 15) / 16 && tile_h == (height + 15) / 16);
     ARG_CHECK(splats && offsets && rgb && alpha && last_ids && n_isects >= 0 && n_isects < 2147483647LL);
     ARG_CHECK(n_isects == 0 || flatten_ids);
-    return st3r_blend_fwd_impl(ctx, (hipStream_t)stream, C, width, height, tile_w, tile_h, splats, offsets,
-                               flatten_ids, n_isects, rgb, alpha, last_ids, true, false);
+    return st3r_blend_fwd_impl(ctx, (hipStream_t)stream,
+                               stage_lists(C, width, height, tile_w, tile_h, splats, offsets, flatten_ids, n_isects), rgb,
+                               alpha, last_ids, true, false);
 }
 
 // ------------------------------------------------------------------------------------
@@ -627,11 +619,12 @@ __global__ __launch_bounds__(256) void k_gather_vtile(int64_t n_pairs, const int
     }
 }
 
-int st3r_blend_bwd_impl(st3r_ctx* ctx, hipStream_t s, int C, int W, int H, int tile_w, int tile_h,
-                        const float* splats, const int32_t* offsets, const int32_t* flat, int64_t n_isects,
-                        const float* alpha, const int32_t* last_ids, const float* v_rgb, const float* v_alpha,
-                        const int32_t* cum, const uint64_t* rects, const uint64_t* rectbase, int tight, int64_t n_pairs,
-                        float* v_splats, bool end_in_offsets, st3r_vtile_ref* defer) {
+int st3r_blend_bwd_impl(st3r_ctx* ctx, hipStream_t s, const RasterOut& ro, const float* alpha, const int32_t* last_ids,
+                        const float* v_rgb, const float* v_alpha, float* v_splats, bool end_in_offsets,
+                        st3r_vtile_ref* defer) {
+    const int C = ro.C, W = ro.W, H = ro.H, tile_w = ro.tile_w, tile_h = ro.tile_h, tight = ro.tight;
+    const int32_t* cum = ro.cum; const uint64_t* rects = ro.rects; const uint64_t* rectbase = ro.rectbase;
+    const int64_t n_isects = ro.n_isects, n_pairs = ro.n_pairs;
     // defer != NULL: the caller's next kernel sums the slots per pair itself (gs_project_bwd.hip); v_splats is not written
     if (defer) *defer = st3r_vtile_ref{cum, nullptr, 0, 0u, nullptr};
     if (n_isects == 0) {
@@ -674,16 +667,16 @@ int st3r_blend_bwd_impl(st3r_ctx* ctx, hipStream_t s, int C, int W, int H, int t
     const unsigned vt_cap = (unsigned)(ctx->slot_bytes[SLOT_VTILE] / (sizeof(float) * VT_STRIDE));
     if (v_alpha)
         hipLaunchKernelGGL(k_blend_bwd<true>, dim3(total), dim3(BLK), 0, s, C, W, H, tile_w, tile_h,
-                           (const float4*)splats, offsets, flat, end_in_offsets ? -1 : (int)n_isects, alpha, last_ids, v_rgb,
+                           (const float4*)ro.splats, ro.offsets, ro.flat, end_in_offsets ? -1 : (int)n_isects, alpha, last_ids, v_rgb,
                            v_alpha, cmask, words, tile_nb, cum, rects, rectbase, tight, vtile, stamp, vt_cap);
     else if (touch)
         hipLaunchKernelGGL((k_blend_bwd<false, true>), dim3(total), dim3(BLK), 0, s, C, W, H, tile_w, tile_h,
-                           (const float4*)splats, offsets, flat, end_in_offsets ? -1 : (int)n_isects, alpha, last_ids, v_rgb,
+                           (const float4*)ro.splats, ro.offsets, ro.flat, end_in_offsets ? -1 : (int)n_isects, alpha, last_ids, v_rgb,
                            v_alpha, cmask, words, tile_nb, cum, reinterpret_cast<const uint64_t*>(touch), rectbase, tight, vtile,
                            stamp, vt_cap);
     else
         hipLaunchKernelGGL(k_blend_bwd<false>, dim3(total), dim3(BLK), 0, s, C, W, H, tile_w, tile_h,
-                           (const float4*)splats, offsets, flat, end_in_offsets ? -1 : (int)n_isects, alpha, last_ids, v_rgb,
+                           (const float4*)ro.splats, ro.offsets, ro.flat, end_in_offsets ? -1 : (int)n_isects, alpha, last_ids, v_rgb,
                            v_alpha, cmask, words, tile_nb, cum, rects, rectbase, tight, vtile, stamp, vt_cap);
     LAUNCH_CHECK();
     if (defer) { *defer = st3r_vtile_ref{cum, vtile, stamp, vt_cap, touch}; return ST3R_OK; }
@@ -713,7 +706,8 @@ ST3R_EXPORT int st3r_gs_blend_bwd(st3r_ctx* ctx, void* stream, int C, int width,
     ARG_CHECK(tile_w == (width + 15) / 16 && tile_h == (height + 15) / 16);
     ARG_CHECK(splats && offsets && alpha && last_ids && v_rgb && v_splats && cum_tiles && n_pairs >= 0);
     ARG_CHECK(n_isects >= 0 && n_isects < 2147483647LL && (n_isects == 0 || flatten_ids));
-    return st3r_blend_bwd_impl(ctx, (hipStream_t)stream, C, width, height, tile_w, tile_h, splats, offsets,
-                               flatten_ids, n_isects, alpha, last_ids, v_rgb, v_alpha, cum_tiles, nullptr, nullptr, 0, n_pairs,
-                               v_splats, false, nullptr);
+    return st3r_blend_bwd_impl(ctx, (hipStream_t)stream,
+                               stage_lists(C, width, height, tile_w, tile_h, splats, offsets, flatten_ids, n_isects, cum_tiles,
+                                           n_pairs),
+                               alpha, last_ids, v_rgb, v_alpha, v_splats, false, nullptr);
 }

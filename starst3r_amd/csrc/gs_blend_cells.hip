@@ -32,6 +32,7 @@
 // byte (one per wave and record) for the positions 2 idx, 2 idx + 1 if their bits are set; when the batch is done the
 // staging thread of a record turns its four flag bytes into four ballots.  (First attempt: every blending lane stored
 // the flag byte itself -- sixteen lanes, one address: the LDS serialises such stores, +0.15 ms.)
+#include "stages.h"
 #include "blend_common.h"
 #include <type_traits>
 
@@ -298,12 +299,12 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(7))) void k
     if (tile_nb && threadIdx.x == 0) tile_nb[g.lb] = nb;
 }
 
-int st3r_blend_fwd_cells_impl(st3r_ctx* ctx, hipStream_t s, int C, int W, int H, int tile_w, int tile_h,
-                              const float* splats, const int32_t* offsets, const int32_t* flat, float* rgb, float* alpha,
+int st3r_blend_fwd_cells_impl(st3r_ctx* ctx, hipStream_t s, const RasterOut& ro, float* rgb, float* alpha,
                               int32_t* last_ids, uint64_t* cmask, int64_t cmask_words, int32_t* tile_nb) {
-    const int total = C * tile_w * tile_h;
-    hipLaunchKernelGGL(k_blend_fwd_cells, dim3(total), dim3(BLK), 0, s, C, W, H, tile_w, tile_h, (const float4*)splats,
-                       offsets, flat, rgb, alpha, last_ids, cmask, cmask_words, tile_nb, ctx->debug_flags & 1);
+    const int total = ro.C * ro.tile_w * ro.tile_h;
+    hipLaunchKernelGGL(k_blend_fwd_cells, dim3(total), dim3(BLK), 0, s, ro.C, ro.W, ro.H, ro.tile_w, ro.tile_h,
+                       (const float4*)ro.splats, ro.offsets, ro.flat, rgb, alpha, last_ids, cmask, cmask_words, tile_nb,
+                       ctx->debug_flags & 1);
     LAUNCH_CHECK();
     return ST3R_OK;
 }

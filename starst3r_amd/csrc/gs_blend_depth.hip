@@ -26,7 +26,7 @@
 // It walks the contribution masks the colour forward left in the ctx, like st3r_gs_blend_bwd.
 #include <type_traits>
 
-#include "common.h"
+#include "stages.h"
 #include "tile_rect.h"
 #include "blend_common.h"
 
@@ -146,14 +146,12 @@ static int forward_hand_off(st3r_ctx* ctx, int C, int tile_w, int tile_h, int64_
     return ST3R_OK;
 }
 
-// end_in_offsets (fused step): offsets has C * tiles + 1 entries and the last one closes the last tile -- the record
-// count may then live on the device, n_isects being a capacity
-int st3r_blend_depth_fwd_impl(st3r_ctx* ctx, hipStream_t s, int C, int W, int H, int tile_w, int tile_h,
-                              const float* splats, const int32_t* offsets, const int32_t* flat, int64_t n_isects,
-                              const int32_t* last_ids, float* depth, bool end_in_offsets) {
+int st3r_blend_depth_fwd_impl(st3r_ctx* ctx, hipStream_t s, const RasterOut& ro, const int32_t* last_ids, float* depth,
+                              bool end_in_offsets) {
     (void)ctx;
-    hipLaunchKernelGGL(k_blend_depth_fwd, dim3(C * tile_w * tile_h), dim3(BLK), 0, s, C, W, H, tile_w, tile_h,
-                       (const float4*)splats, offsets, flat, end_in_offsets ? -1 : (int)n_isects, last_ids, depth);
+    hipLaunchKernelGGL(k_blend_depth_fwd, dim3(ro.C * ro.tile_w * ro.tile_h), dim3(BLK), 0, s, ro.C, ro.W, ro.H, ro.tile_w,
+                       ro.tile_h, (const float4*)ro.splats, ro.offsets, ro.flat, end_in_offsets ? -1 : (int)ro.n_isects,
+                       last_ids, depth);
     LAUNCH_CHECK();
     return ST3R_OK;
 }
@@ -167,8 +165,9 @@ ST3R_EXPORT int st3r_gs_blend_depth_fwd(st3r_ctx* ctx, void* stream, int C, int 
     ARG_CHECK(splats && offsets && alpha && last_ids && depth && n_isects >= 0 && n_isects < 2147483647LL);
     ARG_CHECK(n_isects == 0 || flatten_ids);
     (void)alpha;   // (part of the colour render's result the call is bound to; T is rebuilt from the records)
-    return st3r_blend_depth_fwd_impl(ctx, (hipStream_t)stream, C, width, height, tile_w, tile_h, splats, offsets,
-                                     flatten_ids, n_isects, last_ids, depth, false);
+    return st3r_blend_depth_fwd_impl(ctx, (hipStream_t)stream,
+                                     stage_lists(C, width, height, tile_w, tile_h, splats, offsets, flatten_ids, n_isects),
+                                     last_ids, depth, false);
 }
 
 // ------------------------------------------------------------------------------------
@@ -431,11 +430,12 @@ __global__ __launch_bounds__(256) void k_gather_vtile_depth(int64_t n_pairs, con
     }
 }
 
-int st3r_blend_depth_bwd_impl(st3r_ctx* ctx, hipStream_t s, int C, int W, int H, int tile_w, int tile_h,
-                              const float* splats, const int32_t* offsets, const int32_t* flat, int64_t n_isects,
-                              const float* alpha, const int32_t* last_ids, const float* v_depth, const int32_t* cum,
-                              int64_t n_pairs, float* v_splats, bool end_in_offsets, const uint64_t* rectbase, int tight) {
-    // rectbase / tight (fused step): `cum` belongs to the tight rectangles of the fused emission (see k_blend_bwd)
+int st3r_blend_depth_bwd_impl(st3r_ctx* ctx, hipStream_t s, const RasterOut& ro, const float* alpha,
+                              const int32_t* last_ids, const float* v_depth, float* v_splats, bool end_in_offsets) {
+    // ro.rectbase / ro.tight (fused step): `cum` belongs to the tight rectangles of the fused emission (see k_blend_bwd)
+    const int C = ro.C, tile_w = ro.tile_w, tile_h = ro.tile_h;
+    const int32_t* cum = ro.cum;
+    const int64_t n_isects = ro.n_isects, n_pairs = ro.n_pairs;
     if (n_isects == 0) {
         HIP_TRY(hipMemsetAsync(v_splats, 0, sizeof(float) * ST3R_SPLAT_STRIDE * (size_t)n_pairs, s));
         return ST3R_OK;
@@ -454,9 +454,9 @@ int st3r_blend_depth_bwd_impl(st3r_ctx* ctx, hipStream_t s, int C, int W, int H,
     }
     const int stamp = ++ctx->depth_stamp;
     const unsigned vt_cap = (unsigned)(ctx->slot_bytes[SLOT_VTILE_DEPTH] / (sizeof(float) * DVT_STRIDE));
-    hipLaunchKernelGGL(k_blend_depth_bwd, dim3(C * tile_w * tile_h), dim3(BLK), 0, s, C, W, H, tile_w, tile_h,
-                       (const float4*)splats, offsets, flat, end_in_offsets ? -1 : (int)n_isects, alpha, last_ids, v_depth,
-                       cmask, words, tile_nb, cum, rectbase, tight, (float*)p, stamp, vt_cap);
+    hipLaunchKernelGGL(k_blend_depth_bwd, dim3(C * tile_w * tile_h), dim3(BLK), 0, s, C, ro.W, ro.H, tile_w, tile_h,
+                       (const float4*)ro.splats, ro.offsets, ro.flat, end_in_offsets ? -1 : (int)n_isects, alpha, last_ids,
+                       v_depth, cmask, words, tile_nb, cum, ro.rectbase, ro.tight, (float*)p, stamp, vt_cap);
     LAUNCH_CHECK();
     hipLaunchKernelGGL(k_gather_vtile_depth, dim3(ceil_div(n_pairs, 256)), dim3(256), 0, s, n_pairs, cum,
                        (const float*)p, stamp, vt_cap, (float4*)v_splats);
@@ -473,9 +473,10 @@ ST3R_EXPORT int st3r_gs_blend_depth_bwd(st3r_ctx* ctx, void* stream, int C, int 
     ARG_CHECK(tile_w == (width + 15) / 16 && tile_h == (height + 15) / 16);
     ARG_CHECK(splats && offsets && alpha && last_ids && v_depth && v_splats && cum_tiles && n_pairs >= 0);
     ARG_CHECK(n_isects >= 0 && n_isects < 2147483647LL && (n_isects == 0 || flatten_ids));
-    return st3r_blend_depth_bwd_impl(ctx, (hipStream_t)stream, C, width, height, tile_w, tile_h, splats, offsets,
-                                     flatten_ids, n_isects, alpha, last_ids, v_depth, cum_tiles, n_pairs, v_splats, false,
-                                     nullptr, 0);
+    return st3r_blend_depth_bwd_impl(ctx, (hipStream_t)stream,
+                                     stage_lists(C, width, height, tile_w, tile_h, splats, offsets, flatten_ids, n_isects,
+                                                 cum_tiles, n_pairs),
+                                     alpha, last_ids, v_depth, v_splats, false);
 }
 
 // a += b over the per-pair gradient records (the colour backward's and the depth backward's: float addition, the bits
@@ -588,10 +589,8 @@ ST3R_EXPORT int st3r_gs_depth_bwd(st3r_ctx* ctx, void* stream, int N, int C, con
     if (nb == 0) return ST3R_OK;
     double* part = nullptr;
     if (v_viewmats) {
-        void* p = nullptr;
-        int rc = st3r_arena_get(ctx, SLOT_DEPTH_PART, sizeof(double) * DPOSE_VALS * (size_t)nb * C, &p);
-        if (rc != ST3R_OK) return rc;
-        part = (double*)p;
+        ARENA_GET(SLOT_DEPTH_PART, double, DPOSE_VALS * (size_t)nb * C, dpart);
+        part = dpart;
     }
     hipLaunchKernelGGL(k_depth_bwd, dim3(nb), dim3(256), 0, s, N, C, means, viewmats, splats, v_splats, grads, part);
     LAUNCH_CHECK();

@@ -6,7 +6,7 @@
 //              path's 32-bit (camera, tile) keys in (camera, depth) order);
 //   offsets -- gsplat isect_offset_encode.
 // All integer work: results are bit-exact against oracle/gs_oracle.c.
-#include "common.h"
+#include "stages.h"
 #include "tile_rect.h"
 
 #define SCAN_THREADS 256
@@ -211,9 +211,9 @@ static int chain_ctl(st3r_ctx* ctx, hipStream_t s, int64_t nwords, ChainCtl* c) 
 
 // out = inclusive scan of in (counts) or of the areas of the packed rectangles `rects`; the grand total is left in
 // device memory (*total_dev)
-int st3r_scan_inclusive_i32(st3r_ctx* ctx, hipStream_t s, const int32_t* in, const void* rects, int rect32, int32_t* out,
-                            int64_t n, int32_t** total_dev, uint64_t* pack_out = nullptr, int32_t* total_copy = nullptr,
-                            int32_t* total_host = nullptr) {
+static int st3r_scan_inclusive_i32(st3r_ctx* ctx, hipStream_t s, const int32_t* in, const void* rects, int rect32,
+                                   int32_t* out, int64_t n, int32_t** total_dev, uint64_t* pack_out = nullptr,
+                                   int32_t* total_copy = nullptr, int32_t* total_host = nullptr) {
     const int ntiles = ceil_div(n, SCAN_TILE);
     ChainCtl c;
     int rc = chain_ctl(ctx, s, ntiles, &c);
@@ -286,8 +286,8 @@ __global__ __launch_bounds__(256) void k_isect_emit(int N, int64_t n_pairs, cons
 
 static int bit_length_u32(uint32_t v) { int n = 0; while (v) { ++n; v >>= 1; } return n; }
 
-int st3r_isect_emit_impl(hipStream_t s, int N, int C, const float* splats, const int32_t* cum, int tile_size,
-                         int tile_w, int tile_h, int64_t* isect_ids, int32_t* flatten_ids) {
+static int st3r_isect_emit_impl(hipStream_t s, int N, int C, const float* splats, const int32_t* cum, int tile_size,
+                                int tile_w, int tile_h, int64_t* isect_ids, int32_t* flatten_ids) {
     int64_t n_pairs = (int64_t)N * C;
     if (n_pairs == 0) return ST3R_OK;
     int tile_n_bits = bit_length_u32((uint32_t)(tile_w * tile_h));
@@ -328,8 +328,8 @@ __global__ __launch_bounds__(256) void k_isect_offsets(int64_t n_isects, const i
     }
 }
 
-int st3r_isect_offsets_impl(hipStream_t s, int64_t n_isects, const int64_t* ids, int C, int tile_w, int tile_h,
-                            int32_t* offsets) {
+static int st3r_isect_offsets_impl(hipStream_t s, int64_t n_isects, const int64_t* ids, int C, int tile_w,
+                                   int tile_h, int32_t* offsets) {
     int n_tiles = tile_w * tile_h;
     if (n_isects == 0) {
         HIP_TRY(hipMemsetAsync(offsets, 0, sizeof(int32_t) * (size_t)C * n_tiles, s));

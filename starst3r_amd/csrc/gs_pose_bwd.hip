@@ -250,10 +250,8 @@ ST3R_EXPORT int st3r_gs_viewmat_bwd(st3r_ctx* ctx, void* stream, int N, int C, c
     const int nb = ceil_div(N, 256);
     double* part = nullptr;
     if (nb > 0) {
-        void* p = nullptr;
-        int rc = st3r_arena_get(ctx, SLOT_POSE_PART, sizeof(double) * POSE_VALS * (size_t)nb * C, &p);
-        if (rc != ST3R_OK) return rc;
-        part = (double*)p;
+        ARENA_GET(SLOT_POSE_PART, double, POSE_VALS * (size_t)nb * C, p);
+        part = p;
         hipLaunchKernelGGL(k_viewmat_bwd_part, dim3(nb, C), dim3(256), 0, s, N, means, quats, scales, sh, sh_stride,
                            viewmats, Ks, campos, width, height, (const float4*)splats, (const float4*)v_splats, part);
         LAUNCH_CHECK();

@@ -15,7 +15,7 @@
 // outgrew its buffers moves no camera either.
 // Non-finite gradients are NOT filtered (torch's Adam does not filter them either): a NaN or Inf in G goes through the
 // moments into V and campos of that camera, and stays.  The loss of such a step is non-finite too and says so.
-#include "common.h"
+#include "stages.h"
 
 struct PoseAdamK {
     double lr, b1, b2, eps, bc1, bc2;
@@ -99,8 +99,6 @@ __global__ __launch_bounds__(64) void k_pose_adam(int C, float* __restrict__ vie
     V[12] = 0.0f; V[13] = 0.0f; V[14] = 0.0f; V[15] = 1.0f;
 }
 
-void st3r_adam_guard(st3r_ctx* ctx, const int32_t** count_dev, uint32_t* count_cap);   // adam.hip
-
 static int pose_adam_launch(st3r_ctx* ctx, hipStream_t s, int C, float* viewmats, float* campos, const float* v_viewmats,
                             float* pose_m, float* pose_v, double lr, double b1, double b2, double eps, int step,
                             const float* mask) {
@@ -125,12 +123,6 @@ ST3R_EXPORT int st3r_pose_adam_step(st3r_ctx* ctx, void* stream, int C, float* v
                             eps, step, mask);
 }
 
-int st3r_train_fwd_bwd_impl(st3r_ctx* ctx, void* stream, int N, int C, const float* means, const float* quats,
-                            const float* scales, const float* opacities, const float* sh, int sh_stride,
-                            const float* viewmats, const float* Ks, const float* campos, const float* gt_images, int width,
-                            int height, float ssim_fac, float opac_fac, float scale_fac, float* grads, float* loss_out,
-                            int64_t* stats_host, float* v_viewmats);   // api.hip
-
 // st3r_gs_train_step that also moves the cameras.  Order: forward, loss, blend backward; Gaussian gradients AND the
 // per-camera pose gradient (both at the poses the call started with); Gaussian Adam; pose Adam.  No host round trip of
 // its own: with stats_host == NULL the whole call is asynchronous in steady state, and a step that outgrew its buffers
@@ -152,14 +144,12 @@ ST3R_EXPORT int st3r_gs_train_step_poses(st3r_ctx* ctx, void* stream, int N, int
     }
     float* v_viewmats = v_viewmats_out;
     if (!v_viewmats) {
-        void* p = nullptr;
-        int rc = st3r_arena_get(ctx, SLOT_POSE_GRAD, sizeof(float) * 16 * (size_t)C, &p);
-        if (rc) return rc;
-        v_viewmats = (float*)p;
+        ARENA_GET(SLOT_POSE_GRAD, float, 16 * (size_t)C, own);
+        v_viewmats = own;
     }
-    int rc = st3r_train_fwd_bwd_impl(ctx, stream, N, C, means, quats, scales, opacities, sh, sh_stride, viewmats, Ks, campos,
-                                     gt_images, width, height, ssim_fac, opac_fac, scale_fac, grads, loss_out, stats_host,
-                                     v_viewmats);
+    int rc = st3r_train_fwd_bwd_impl(ctx, (hipStream_t)stream, GsParams{N, means, quats, scales, opacities, sh, sh_stride},
+                                     GsViews{C, width, height, viewmats, Ks, campos}, gt_images, ssim_fac, opac_fac,
+                                     scale_fac, grads, loss_out, stats_host, v_viewmats);
     if (rc) return rc;
     rc = st3r_adam_step(ctx, stream, N, means, quats, scales, opacities, sh, sh_stride, grads, m, v, lr, beta1, beta2, eps,
                         step);

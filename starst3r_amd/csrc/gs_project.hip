@@ -9,7 +9,7 @@
 // integer outputs that must be bit-exact against oracle/gs_oracle.c, so every float
 // operation below is a single IEEE binary32 op in a fixed order (sums of three products
 // left to right; 1/x and sqrt correctly rounded -- hipcc's default for HIP).
-#include "common.h"
+#include "stages.h"
 #include "tile_rect.h"
 
 #define CAM_STRIDE 32
@@ -278,13 +278,12 @@ __global__ __launch_bounds__(256) void k_reg_reduce(int n_blocks, const double* 
 
 // depth_keys/depth_vals (optional, [C*N]): per-pair (camera | depth bits) key and pair id for the
 // two-level sort of the fused path
-int st3r_project_impl(st3r_ctx* ctx, hipStream_t s, int N, int C, const float* means, const float* quats, const float* scales,
-                      const float* opacities, const float* sh, int sh_stride, const float* viewmats, const float* Ks,
-                      const float* campos, int width, int height, int tile_size, float eps2d, float near_plane,
-                      float far_plane, float radius_clip, float* splats, int32_t* tiles_per_gauss, double* reg_sums,
-                      uint64_t* depth_keys, int32_t* depth_vals, int tight, uint32_t key_base, void* rects, int rect32,
-                      int reg_overwrite, double* zero_ptr, int zero_n, uint32_t* krange) {
+int st3r_project_impl(st3r_ctx* ctx, hipStream_t s, const GsParams& g, const GsViews& v, int tile_size, float eps2d,
+                      float near_plane, float far_plane, float radius_clip, float* splats, int32_t* tiles_per_gauss,
+                      double* reg_sums, uint64_t* depth_keys, int32_t* depth_vals, int tight, uint32_t key_base, void* rects,
+                      int rect32, int reg_overwrite, double* zero_ptr, int zero_n, uint32_t* krange) {
     // krange != NULL (needs reg_sums): segment keys + key range for the segmented level-1 sort (see k_reg_reduce)
+    const int N = g.N, C = v.C, width = v.W, height = v.H;
     if (N == 0) {
         if (reg_sums && reg_overwrite) HIP_TRY(hipMemsetAsync(reg_sums, 0, sizeof(double) * 4, s));
         if (zero_ptr && zero_n > 0) HIP_TRY(hipMemsetAsync(zero_ptr, 0, sizeof(double) * (size_t)zero_n, s));
@@ -295,20 +294,16 @@ int st3r_project_impl(st3r_ctx* ctx, hipStream_t s, int N, int C, const float* m
     size_t shmem = (size_t)C * CAM_STRIDE * sizeof(float);
     double* reg_part = nullptr;
     if (reg_sums) {
-        void* p;
-        int rc = st3r_arena_get(ctx, SLOT_REG_PART, sizeof(double) * 4 * (size_t)grid.x, &p);
-        if (rc) return rc;
-        reg_part = (double*)p;
+        ARENA_GET(SLOT_REG_PART, double, 4 * (size_t)grid.x, p);
+        reg_part = p;
     }
     uint32_t* krange_part = nullptr;
     if (krange && reg_sums) {
-        void* p;
-        int rc = st3r_arena_get(ctx, SLOT_KRANGE_PART, sizeof(uint32_t) * 2 * (size_t)grid.x, &p);
-        if (rc) return rc;
-        krange_part = (uint32_t*)p;
+        ARENA_GET(SLOT_KRANGE_PART, uint32_t, 2 * (size_t)grid.x, p);
+        krange_part = p;
     }
-    hipLaunchKernelGGL(k_project_sh_fwd, grid, block, shmem, s, N, C, means, quats, scales, opacities, sh, sh_stride,
-                       viewmats, Ks, campos, width, height, tile_size, tile_w, tile_h, eps2d, near_plane, far_plane,
+    hipLaunchKernelGGL(k_project_sh_fwd, grid, block, shmem, s, N, C, g.means, g.quats, g.scales, g.opacities, g.sh,
+                       g.sh_stride, v.viewmats, v.Ks, v.campos, width, height, tile_size, tile_w, tile_h, eps2d, near_plane, far_plane,
                        radius_clip, (float4*)splats, tiles_per_gauss, reg_part, depth_keys, depth_vals, tight, key_base,
                        rects, rect32, krange_part);
     if (reg_sums)
@@ -328,7 +323,7 @@ ST3R_EXPORT int st3r_gs_project_sh(st3r_ctx* ctx, void* stream, int N, int C, co
                                    int32_t* tiles_per_gauss, double* reg_sums) {
     ARG_CHECK(ctx && N >= 0 && C > 0 && C <= ST3R_MAX_VIEWS && sh_stride >= 12 && width > 0 && height > 0 && tile_size > 0);
     ARG_CHECK(means && quats && scales && opacities && sh && viewmats && Ks && campos && splats && tiles_per_gauss);
-    return st3r_project_impl(ctx, (hipStream_t)stream, N, C, means, quats, scales, opacities, sh, sh_stride, viewmats, Ks,
-                             campos, width, height, tile_size, eps2d, near_plane, far_plane, radius_clip, splats,
+    return st3r_project_impl(ctx, (hipStream_t)stream, GsParams{N, means, quats, scales, opacities, sh, sh_stride},
+                             GsViews{C, width, height, viewmats, Ks, campos}, tile_size, eps2d, near_plane, far_plane, radius_clip, splats,
                              tiles_per_gauss, reg_sums, nullptr, nullptr, 0, 0u, nullptr, 0, 0, nullptr, 0, nullptr);
 }

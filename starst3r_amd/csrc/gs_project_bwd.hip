@@ -13,7 +13,7 @@
 // through LDS, then lane = pair adds its own rows, the next slots in flight), per wave and camera, and the nine sums go straight
 // into the chain rule instead of through 48 bytes per pair of HBM each way (0.58 GB per step at SYNTH-1M).  Same sums in the
 // same order: bit-identical gradients.
-#include "common.h"
+#include "stages.h"
 #include "blend_common.h"
 
 #define CAM_STRIDE 32
@@ -389,25 +389,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
     for (int i = 0; i < 12; ++i) gsh[(int64_t)gw * 12 + i] = v_k[i];
 }
 
-int st3r_project_sh_bwd_impl(hipStream_t s, int N, int C, const float* means, const float* quats, const float* scales,
-                             const float* opacities, const float* sh, int sh_stride, const float* viewmats,
-                             const float* Ks, const float* campos, int width, int height, float eps2d,
-                             const float* splats, const float* v_splats, float reg_views, float opac_fac,
-                             float scale_fac, float* grads, bool accumulate, int g_begin, int g_end, bool range_major,
-                             const st3r_vtile_ref* slots) {
+int st3r_project_sh_bwd_impl(hipStream_t s, const GsParams& g, const GsViews& v, float eps2d, const float* splats,
+                             const float* v_splats, float reg_views, float opac_fac, float scale_fac, float* grads,
+                             bool accumulate, int g_begin, int g_end, bool range_major, const st3r_vtile_ref* slots) {
+    const int N = g.N, C = v.C;
     if (g_end < 0) g_end = N;
     if (N == 0 || g_end <= g_begin) return ST3R_OK;
     float reg_o_k = reg_views * opac_fac / (float)N;
     float reg_s_k = reg_views * scale_fac / (3.0f * (float)N);
     size_t shmem = (size_t)C * CAM_STRIDE * sizeof(float);
     if (slots)   // fused training calls: the pair sums are gathered from the backward's slots in this kernel
-        hipLaunchKernelGGL(k_project_sh_bwd<true>, dim3(ceil_div(g_end - g_begin, 256)), dim3(256), shmem, s, N, C, means,
-                           quats, scales, opacities, sh, sh_stride, viewmats, Ks, campos, width, height, eps2d,
+        hipLaunchKernelGGL(k_project_sh_bwd<true>, dim3(ceil_div(g_end - g_begin, 256)), dim3(256), shmem, s, N, C, g.means,
+                           g.quats, g.scales, g.opacities, g.sh, g.sh_stride, v.viewmats, v.Ks, v.campos, v.W, v.H, eps2d,
                            (const float4*)splats, (const float4*)nullptr, reg_o_k, reg_s_k, grads, accumulate ? 1 : 0, g_begin,
                            g_end, range_major ? 1 : 0, slots->cum, slots->vtile, slots->stamp, slots->vt_cap, slots->touch);
     else
-        hipLaunchKernelGGL(k_project_sh_bwd<false>, dim3(ceil_div(g_end - g_begin, 256)), dim3(256), shmem, s, N, C, means,
-                           quats, scales, opacities, sh, sh_stride, viewmats, Ks, campos, width, height, eps2d,
+        hipLaunchKernelGGL(k_project_sh_bwd<false>, dim3(ceil_div(g_end - g_begin, 256)), dim3(256), shmem, s, N, C, g.means,
+                           g.quats, g.scales, g.opacities, g.sh, g.sh_stride, v.viewmats, v.Ks, v.campos, v.W, v.H, eps2d,
                            (const float4*)splats, (const float4*)v_splats, reg_o_k, reg_s_k, grads, accumulate ? 1 : 0, g_begin,
                            g_end, range_major ? 1 : 0, (const int32_t*)nullptr, (const float*)nullptr, 0, 0u, (const uint32_t*)nullptr);
     LAUNCH_CHECK();
@@ -422,7 +420,7 @@ ST3R_EXPORT int st3r_gs_project_sh_bwd(st3r_ctx* ctx, void* stream, int N, int C
                                        float opac_fac, float scale_fac, float* grads) {
     ARG_CHECK(ctx && N >= 0 && C > 0 && C <= ST3R_MAX_VIEWS && sh_stride >= 12);
     ARG_CHECK(means && quats && scales && opacities && sh && viewmats && Ks && campos && splats && v_splats && grads);
-    return st3r_project_sh_bwd_impl((hipStream_t)stream, N, C, means, quats, scales, opacities, sh, sh_stride, viewmats,
-                                    Ks, campos, width, height, eps2d, splats, v_splats, reg_views, opac_fac, scale_fac,
+    return st3r_project_sh_bwd_impl((hipStream_t)stream, GsParams{N, means, quats, scales, opacities, sh, sh_stride},
+                                    GsViews{C, width, height, viewmats, Ks, campos}, eps2d, splats, v_splats, reg_views, opac_fac, scale_fac,
                                     grads, false, 0, -1, false, nullptr);
 }

@@ -13,7 +13,7 @@
 //   backward: v_x = k_l1*sign(x-y) + k_ss*( G*D0 + 2x G*D1 + y G*D2 )   (G symmetric).
 // k_ssim_fwd is the forward alone (value-only calls); k_ssim_fused runs both with D kept in LDS (see there).
 // The window never touches padding for interior outputs, so reflect-padding is not needed.
-#include "common.h"
+#include "stages.h"
 
 #define LW 64                 // strip width in pixels
 #define LT (LW * 3)           // threads per workgroup: one per (column, channel)

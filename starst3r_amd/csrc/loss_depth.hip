@@ -14,7 +14,7 @@
 // Sums: every thread adds its pixels in double, the wave meets in a butterfly, the four waves in order, one double partial
 // per workgroup; a second launch (one workgroup per view) adds a view's partials the same way.  No atomics, a fixed order for a given shape: the same inputs give the same bits.
 // n_c depends on the weights alone: the fused step computes it once per registration (st3r_ctx_set_depth_prior).
-#include "common.h"
+#include "stages.h"
 
 #define DP_T 256          // threads per workgroup
 #define DP_ALIGN 1024     // chunk granularity in pixels: one 16-byte access per thread
@@ -130,10 +130,8 @@ static void dp_grid(int C, int64_t HW, int* blocks, int64_t* chunk) {
 static bool dp_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 static int dp_partials(st3r_ctx* ctx, int C, int blocks, double** part) {
-    void* p = nullptr;
-    int rc = st3r_arena_get(ctx, SLOT_DPRIOR_PART, sizeof(double) * (size_t)C * blocks, &p);
-    if (rc) return rc;
-    *part = (double*)p;
+    ARENA_GET(SLOT_DPRIOR_PART, double, (size_t)C * blocks, p);
+    *part = p;
     return ST3R_OK;
 }
 
@@ -178,12 +176,11 @@ int st3r_depth_prior_loss_impl(st3r_ctx* ctx, hipStream_t s, int C, int H, int W
     return ST3R_OK;
 }
 
-// The registered prior that belongs to the C views at `gt` (api.hip): *prior = NULL if there is none (no registration,
+// The registered prior that belongs to the C views at `gt` (fused_step.hip): out->prior = NULL if there is none (no registration,
 // depth_fac == 0, another image size, or not a whole-view offset into the registered images).  The n_c of the
 // registration are computed by the first call that gets here, on its stream.
-int st3r_depth_prior_for(st3r_ctx* ctx, hipStream_t s, const float* gt, int C, int H, int W, const float** prior,
-                         const float** weight, const double** norm, float* depth_fac) {
-    *prior = nullptr; *weight = nullptr; *norm = nullptr; *depth_fac = 0.f;
+int st3r_depth_prior_for(st3r_ctx* ctx, hipStream_t s, const float* gt, int C, int H, int W, DepthPrior* out) {
+    *out = DepthPrior{};
     if (!ctx->dp_depth || ctx->dp_fac == 0.f || H != ctx->dp_h || W != ctx->dp_w) return ST3R_OK;
     const int64_t img = (int64_t)H * W * 3, HW = (int64_t)H * W;
     if (gt < ctx->dp_gt || (gt - ctx->dp_gt) % img != 0) return ST3R_OK;
@@ -197,8 +194,7 @@ int st3r_depth_prior_for(st3r_ctx* ctx, hipStream_t s, const float* gt, int C, i
         if (rc) return rc;
         ctx->dp_norm_valid = 1;
     }
-    *prior = ctx->dp_depth + c0 * HW; *weight = ctx->dp_weight + c0 * HW; *norm = (const double*)p + c0;
-    *depth_fac = ctx->dp_fac;
+    *out = DepthPrior{ctx->dp_depth + c0 * HW, ctx->dp_weight + c0 * HW, (const double*)p + c0, ctx->dp_fac};
     return ST3R_OK;
 }
 

@@ -387,10 +387,7 @@ int sort_pairs(st3r_ctx* ctx, hipStream_t s, int64_t n, int begin_bit, int end_b
     const bool need_tmp = passes > 1;
     const size_t tk_bytes = need_tmp ? align256(sizeof(K) * (size_t)n) : 0;
     const size_t tv_bytes = need_tmp && vals_in ? align256(sizeof(int32_t) * (size_t)n) : 0;
-    void* p;
-    int rc = st3r_arena_get(ctx, SLOT_SORT_TMP, meta_bytes + tk_bytes + tv_bytes, &p);
-    if (rc) return rc;
-    char* base = (char*)p;
+    ARENA_GET(SLOT_SORT_TMP, char, meta_bytes + tk_bytes + tv_bytes, base);
     uint32_t* hist = (uint32_t*)base;
     uint32_t* counters = hist + HIST_COPIES * MAX_PASSES * RADIX;
     u64* status = (u64*)(base + hist_bytes);
@@ -441,10 +438,7 @@ int sort_pairs_seg(st3r_ctx* ctx, hipStream_t s, int64_t seg_n, int n_seg, const
     const size_t status_bytes = sizeof(u64) * (size_t)PASSES * (size_t)ntiles * RADIX;
     const size_t meta_bytes = hist_bytes + align256(status_bytes);
     const size_t tk_bytes = align256(sizeof(K) * (size_t)n), tv_bytes = align256(sizeof(int32_t) * (size_t)n);
-    void* p;
-    int rc = st3r_arena_get(ctx, SLOT_SORT_TMP, meta_bytes + tk_bytes + tv_bytes, &p);
-    if (rc) return rc;
-    char* base = (char*)p;
+    ARENA_GET(SLOT_SORT_TMP, char, meta_bytes + tk_bytes + tv_bytes, base);
     uint32_t* hist = (uint32_t*)base;
     uint32_t* counters = hist + (size_t)n_seg * MAX_PASSES * RADIX;
     u64* status = (u64*)(base + hist_bytes);

@@ -1,0 +1,117 @@
+// Internal interface between the translation units of libst3r_hip.so: every function that is defined in one .hip file
+// and called from another is declared here, once, and the defining file includes this header too -- a definition that
+// drifts from its declaration is a compile error, not a link error.  (radix_sort.h does the same for the sort.)
+// A launcher nobody outside its file calls is static there and has no line here.
+#pragma once
+#include "common.h"
+
+// ---- argument bundles of the internal calls (the exported C functions keep their flat lists and fill these) ----
+struct GsParams {   // the Gaussians: [N,3] [N,4] [N,3] [N] [N,sh_stride]
+    int N;
+    const float *means, *quats, *scales, *opacities, *sh;
+    int sh_stride;
+};
+
+struct GsViews {   // C views of W x H pixels: [C,4,4] [C,3,3] [C,3]
+    int C, W, H;
+    const float *viewmats, *Ks, *campos;
+    GsViews slice(int c0, int c1) const { return {c1 - c0, W, H, viewmats + 16 * c0, Ks + 9 * c0, campos + 3 * c0}; }
+};
+
+// What the front end of a fused call (project -> scan -> emit -> sort -> offsets, fused_step.hip) leaves for the blend
+// kernels; the stand-alone blend entry points fill one from their arguments (cum / rects / rectbase they do not have
+// stay NULL, tight 0).
+struct RasterOut {
+    int C, W, H, tile_w, tile_h;
+    const float* splats; const int32_t *offsets, *flat, *cum; const uint64_t *rects, *rectbase;
+    int tight;          // `cum` counts the tight rectangles of the fused emission (see k_blend_bwd)
+    int64_t n_pairs;    // N * C
+    // n_isects: the slot count (sum of the rectangle areas) = capacity of everything indexed by record or slot;
+    // n_records: the records emitted (= n_isects on the synchronous path), -1 while the count stays on the device
+    int64_t n_isects, n_records, n_isects_ref, n_visible;
+};
+
+// the lists of a stand-alone blend call (stage API): no rectangles, and a pair scan only for the backward
+static inline RasterOut stage_lists(int C, int W, int H, int tile_w, int tile_h, const float* splats, const int32_t* offsets,
+                                    const int32_t* flat, int64_t n_isects, const int32_t* cum = nullptr,
+                                    int64_t n_pairs = 0) {
+    return RasterOut{C, W, H, tile_w, tile_h, splats, offsets, flat, cum, nullptr, nullptr, 0, n_pairs, n_isects, n_isects,
+                     n_isects, -1};
+}
+
+// the registered depth prior of a set of views (loss_depth.hip); prior == NULL: none applies
+struct DepthPrior { const float* prior; const float* weight; const double* norm; float fac; };
+
+// ---- api.hip, fused_step.hip, comm.hip ----
+// The 16 device words next to the fused steps: [0] record count of an asynchronous step (k_adam compares it with the
+// step's capacity), [4] status word of an exchanged step (comm.hip).  Zeroed when allocated.
+int st3r_counts_buffer(st3r_ctx* ctx, hipStream_t s, int32_t** out);
+int st3r_count_settle(st3r_ctx* ctx);
+// st3r_gs_train_fwd_bwd, and with v_viewmats != NULL ([C,4,4]) the pose gradient of every view next to it
+int st3r_train_fwd_bwd_impl(st3r_ctx* ctx, hipStream_t s, const GsParams& g, const GsViews& v, const float* gt_images,
+                            float ssim_fac, float opac_fac, float scale_fac, float* grads, float* loss_out,
+                            int64_t* stats_host, float* v_viewmats);
+int st3r_peer_status_settle(st3r_ctx* ctx);
+
+// ---- gs_project.hip, gs_project_bwd.hip ----
+int st3r_project_impl(st3r_ctx* ctx, hipStream_t s, const GsParams& g, const GsViews& v, int tile_size, float eps2d,
+                      float near_plane, float far_plane, float radius_clip, float* splats, int32_t* tiles_per_gauss,
+                      double* reg_sums, uint64_t* depth_keys, int32_t* depth_vals, int tight, uint32_t key_base, void* rects,
+                      int rect32, int reg_overwrite, double* zero_ptr, int zero_n, uint32_t* krange);
+int st3r_project_sh_bwd_impl(hipStream_t s, const GsParams& g, const GsViews& v, float eps2d, const float* splats,
+                             const float* v_splats, float reg_views, float opac_fac, float scale_fac, float* grads,
+                             bool accumulate, int g_begin, int g_end, bool range_major, const st3r_vtile_ref* slots);
+
+// ---- gs_isect.hip, gs_sort.hip ----
+int st3r_isect_scan_impl(st3r_ctx* ctx, hipStream_t s, int64_t n_pairs, const int32_t* tiles, int32_t* cum,
+                         int64_t* n_isects_host, const void* pack_rects, int rect32, uint64_t* pack_out,
+                         int32_t** total_dev_out, int32_t* total_copy, int32_t* total_host);
+int st3r_isect_emit_chain_impl(st3r_ctx* ctx, hipStream_t s, int N, int C, const int32_t* perm, const void* rects,
+                               int rect32, int tile_w, int tile_h, uint32_t* tile_keys, int32_t* vals, int64_t cap);
+int st3r_records_prepare_impl(hipStream_t s, int N, int C, const float* splats, int tile_size, int tile_w, int tile_h,
+                              int tight, int32_t* tiles, uint64_t* depth_keys, int32_t* depth_vals, uint32_t key_base,
+                              void* rects, int rect32);
+int st3r_isect_offsets32_impl(hipStream_t s, int64_t n_isects, const uint32_t* keys, int C, int tile_w, int tile_h,
+                              int32_t* offsets, const int32_t* n_dev);
+int st3r_sort_tile_impl(st3r_ctx* ctx, hipStream_t s, int64_t n, int end_bit, uint32_t* keys_in, int32_t* vals_in,
+                        uint32_t* keys_out, int32_t* vals_out, const int32_t* n_dev);
+
+// ---- gs_blend.hip, gs_blend_cells.hip, gs_blend_depth.hip ----
+// end_in_offsets (fused calls): ro.offsets has C * tiles + 1 entries and the last one closes the last tile -- the record
+// count may then live on the device, ro.n_isects being a capacity
+int st3r_blend_fwd_impl(st3r_ctx* ctx, hipStream_t s, const RasterOut& ro, float* rgb, float* alpha, int32_t* last_ids,
+                        bool for_backward, bool end_in_offsets);
+int st3r_blend_fwd_cells_impl(st3r_ctx* ctx, hipStream_t s, const RasterOut& ro, float* rgb, float* alpha,
+                              int32_t* last_ids, uint64_t* cmask, int64_t cmask_words, int32_t* tile_nb);
+int st3r_blend_bwd_impl(st3r_ctx* ctx, hipStream_t s, const RasterOut& ro, const float* alpha, const int32_t* last_ids,
+                        const float* v_rgb, const float* v_alpha, float* v_splats, bool end_in_offsets,
+                        st3r_vtile_ref* defer);
+int st3r_gather_vtile_impl(hipStream_t s, int64_t n_pairs, const st3r_vtile_ref* slots, float* v_splats);
+int st3r_blend_depth_fwd_impl(st3r_ctx* ctx, hipStream_t s, const RasterOut& ro, const int32_t* last_ids, float* depth,
+                              bool end_in_offsets);
+int st3r_blend_depth_bwd_impl(st3r_ctx* ctx, hipStream_t s, const RasterOut& ro, const float* alpha,
+                              const int32_t* last_ids, const float* v_depth, float* v_splats, bool end_in_offsets);
+int st3r_add_pairs_impl(hipStream_t s, int64_t n_pairs, float* a, const float* b);
+
+// ---- loss.hip, loss_depth.hip ----
+int st3r_loss_impl(st3r_ctx* ctx, hipStream_t s, int C, int H, int W, const float* render, const float* gt,
+                   float w_l1, float w_ssim, double* sums, float* v_render, bool sums_cleared);
+int st3r_depth_prior_for(st3r_ctx* ctx, hipStream_t s, const float* gt, int C, int H, int W, DepthPrior* out);
+int st3r_depth_prior_loss_impl(st3r_ctx* ctx, hipStream_t s, int C, int H, int W, const float* depth, const float* alpha,
+                               const float* prior, const float* weight, const double* norm, int norm_stride,
+                               float depth_fac, double* sums, int sums_stride, float* v_depth, float* v_alpha);
+
+// ---- adam.hip ----
+// i0 < 0: the whole buffer.  [g0, g1) a proper sub-range of the Gaussians: that range instead of [i0, i1).
+int st3r_adam_impl(hipStream_t s, int N, float* means, float* quats, float* scales, float* opacities, float* sh,
+                   int sh_stride, const float* grads, float* m, float* v, double lr, double b1, double b2,
+                   double eps, int step, const int32_t* count_dev, uint32_t count_cap, const int32_t* status_dev, int64_t i0,
+                   int64_t i1, int64_t g0, int64_t g1, float* pstage, const float* gstage, float* grads_out);
+int st3r_params_from_stage_impl(hipStream_t s, int N, float* means, float* quats, float* scales, float* opacities,
+                                float* sh, int sh_stride, const float* pstage, int64_t i0, int64_t i1, int64_t lim,
+                                const int32_t* count_dev, uint32_t count_cap, const int32_t* status_dev);
+int st3r_params_from_peers_impl(hipStream_t s, int N, float* means, float* quats, float* scales, float* opacities,
+                                float* sh, int sh_stride, const float* const* tab, int r, int64_t q, int64_t lim,
+                                const int32_t* status_dev);
+// the device-side guard of an asynchronous step that is still in flight (see k_adam)
+void st3r_adam_guard(st3r_ctx* ctx, const int32_t** count_dev, uint32_t* count_cap);

@@ -1,5 +1,5 @@
 """Training against depth maps: st3r_loss_depth_prior (loss_depth.hip), st3r_ctx_set_depth_prior inside the fused steps
-(api.hip) and run_3dgs_optim(depth_fac=...).
+(fused_step.hip) and run_3dgs_optim(depth_fac=...).
 
 References: float64 torch for the loss kernel; for the fused gradient the unfused chain -- render_3dgs(..., "RGB+ED")
 through autograd, ops.loss_l1_ssim, the depth term in torch -- and the float64 dense renderer of test_gpu_depth.py, which
@@ -433,6 +433,32 @@ def test_chunked_views_give_the_depth_gradient_of_the_whole_call():
     ctx = ops.Context("cuda:0")
     G, vvm, loss, _ = _fused_step(ctx, R, poses=True, debug=32)
     _check_against_reference("many, two view chunks", R, G, vvm, loss)
+    ctx.close()
+
+
+def test_chunked_depth_pose_step_has_the_bits_of_the_whole_call():
+    """Depth prior + poses + two view chunks (debug flag 32) against the same step in one pass, bit for bit where the
+    result is per view: a view belongs to one chunk, which runs the same kernels on that view's tiles, pairs and
+    (camera, block) partials, so v_viewmats -- row 2 with the depth backward's addition included -- must not change.
+    The loss is the float32 store of a double sum over the per-view sums, taken in view order either way; the per-view
+    sums themselves are double accumulations whose order may depend on the launch (a relative 1e-15), so the two stores
+    are the same float or neighbours: one float32 ulp, 2^-23 relative.  The parameter gradients of the chunked call are
+    sums of chunk gradients (another association of the same float terms): printed, pinned by the test above."""
+    from starst3r_amd import ops
+    ctx = ops.Context("cuda:0")
+    N, V, W, H = 300, 3, 40, 24   # 3 x 2 tiles with ragged edges; chunks of 1 and 2 views
+    g, w2c, Ks = synth.make_scene(N, V, W, H, seed=7, scale_lo=0.02, scale_hi=0.08)
+    P, vm, K, campos, gt = _setup(ctx, g, w2c, Ks, W, H)
+    Z, wt, _ = _synthetic_prior(ctx, P, vm, K, W, H)
+    assert float(wt.sum()) > 0
+    R = dict(P=P, vm=vm, K=K, campos=campos, gt=gt, Z=Z, wt=wt, W=W, H=H)
+    _, vvm, loss, flat = _fused_step(ctx, R, poses=True)
+    _, vvm_c, loss_c, flat_c = _fused_step(ctx, R, poses=True, debug=32)
+    assert float(vvm.abs().max()) > 0 and float(vvm[:, 2].abs().max()) > 0
+    print("chunked vs whole: loss %.9g %.9g, gradients %s" % (loss_c, loss, "same bits" if _same_bits(flat, flat_c)
+          else "max rel %.1e" % _rel(flat_c, flat)))
+    assert _same_bits(vvm, vvm_c), (vvm - vvm_c).abs().max()
+    assert abs(loss_c - loss) <= 2.0 ** -23 * abs(loss), (loss_c, loss)
     ctx.close()
 
 
