@@ -14,6 +14,7 @@ pytestmark = pytest.mark.gpu
 
 from oracle import gs_oracle as go
 from st3r_synth import synth
+import loss_adam_cases as lac
 
 
 @pytest.fixture(scope="module")
@@ -428,24 +429,12 @@ def test_adam_vs_oracle_and_torch(ctx):
     ref = {k: v.copy() for k, v in g0.items()}
     m = torch.zeros(23 * N, device="cuda:0"); v = torch.zeros(23 * N, device="cuda:0")
     m_o = np.zeros(23 * N, np.float32); v_o = np.zeros(23 * N, np.float32)
-    blocks = [("means", 3), ("quats", 4), ("scales", 3), ("opacities", 1)]
     for step in range(1, 5):
-        gr = (rng.standard_normal(23 * N) * 10.0 ** rng.integers(-5, 1, 23 * N)).astype(np.float32)
-        ops.adam_step(ctx, P, dev(gr), m, v, 1e-3, 0.9, 0.999, 1e-8, step)
-        off = 0
-        for name, w in blocks:
-            sl = slice(off, off + w * N)
-            p = ref[name].reshape(-1); mm = m_o[sl]; vv = v_o[sl]
-            go.adam(p, gr[sl], mm, vv, 1e-3, 0.9, 0.999, 1e-8, step)
-            m_o[sl] = mm; v_o[sl] = vv
-            off += w * N
-        p = np.ascontiguousarray(ref["shN"][:, :4, :]).reshape(-1); sl = slice(off, off + 12 * N)
-        mm = m_o[sl]; vv = v_o[sl]
-        go.adam(p, gr[sl], mm, vv, 1e-3, 0.9, 0.999, 1e-8, step)
-        m_o[sl] = mm; v_o[sl] = vv
-        ref["shN"][:, :4, :] = p.reshape(N, 4, 3)
+        gr = lac.wide_range_grads(rng, 23 * N)
+        ops.adam_step(ctx, P, dev(gr), m, v, *lac.ADAM_HP, step)
+        lac.adam_oracle_step(ref, m_o, v_o, gr, step)   # (the block layout and the SH rows: loss_adam_cases.py)
     torch.cuda.synchronize()
-    for name in ("means", "quats", "scales", "opacities", "shN"):
+    for name in lac.ADAM_NAMES:
         np.testing.assert_allclose(P[name].cpu().numpy(), ref[name], rtol=0, atol=3e-7, err_msg=name)
     assert np.array_equal(P["shN"].cpu().numpy()[:, 4:], g0["shN"][:, 4:])  # rows 4..23 untouched
     np.testing.assert_allclose(m.cpu().numpy(), m_o, rtol=1e-5, atol=1e-12)

@@ -15,6 +15,7 @@ from oracle import gs_oracle as go
 from oracle import gs_torch_ref as tr
 from st3r_synth import synth
 from kat_scenes import cam_front as _cam_front, sh_const as _sh_const, radius_kat_scene as _radius_kat_scene
+import loss_adam_cases as lac
 
 
 def test_single_gaussian_kat(oracle_built):
@@ -192,6 +193,24 @@ def test_ssim_identities_and_autograd(oracle_built):
     _, ssc, _ = go.l1_ssim(np.full((24, 24, 3), a, np.float32), np.full((24, 24, 3), b, np.float32), want_grad=False)
     c1 = 1e-4
     assert abs(ssc - (2 * a * b + c1) / (a * a + b * b + c1)) < 1e-5
+
+
+@pytest.mark.parametrize("shape", [(11, 11), (12, 70), (40, 65), (130, 70)])
+def test_ssim_autograd_on_structured_images(oracle_built, shape):
+    """The oracle on the inputs the GPU loss tests use (loss_adam_cases.structured: black render regions, flat saturated
+    ground truth, pixels with x == y) against float64 autograd of the torch restatement, at the bounds of
+    test_ssim_identities_and_autograd.  No constant non-zero render: see structured()."""
+    H, W = shape
+    x, y = lac.structured(H, W, seed=H * 1000 + W)
+    low = y[H // 2:]
+    assert (x[:, :W // 3] == 0).all() and (x[:, W // 3:] > 0).all()          # black left third
+    assert np.isin(low[low != x[H // 2:]], (0.0, 1.0)).all()                  # flat lower half of the ground truth
+    assert (x[1::4, 2::5] == y[1::4, 2::5]).all() and y.min() == 0 and y.max() == 1
+    l1, ss, vr = go.l1_ssim(x, y, lac.W_L1, lac.W_SSIM)
+    l1_t, ss_t, g_t = lac.torch_loss_grad(x, y, torch.float64)
+    assert abs(l1 - l1_t) < 1e-7 and abs(ss - ss_t) < 1e-7
+    np.testing.assert_allclose(vr, g_t, rtol=1e-4, atol=1e-9)
+    print(f"structured {shape}: of max / element-wise {lac.grad_errors(vr, g_t)}")
 
 
 def test_adam_matches_torch_optim(oracle_built):
