@@ -379,6 +379,11 @@ int st3r_align_run_opts(st3r_ctx* ctx, void* stream, int C, int G, int n_anchors
 int st3r_nn_dot_argmax(st3r_ctx* ctx, void* stream, const float* queries, int n, const float* db, int m, int dim,
                        int32_t* nn_out, float* score_out);
 
+/* The segment plan both entry points of path A use for n (> 0) queries against m (> 0) rows: the 32-row tiles of the
+ * db are cut into *S segments of *tiles_per_seg tiles, one wave per (64 queries, segment).  Host arithmetic only (no
+ * context, no GPU): it is here so that tests can assert which paths of the kernel their shapes reach. */
+int st3r_nn_plan(int n, int m, int* S, int* tiles_per_seg);
+
 /* The whole reciprocal iteration of fast_reciprocal_NNs(A, B, subsample_or_initxy1=subsample, dist='dot')
  * (starster/reconstruct.py:97 passes subsample=8) resident on the device, no host synchronisation:
  *   seeds = flat indices x + W1*y on the grid np.mgrid[S//2:H1:S, S//2:W1:S]   (n = st3r_recip_nn_seed_count)

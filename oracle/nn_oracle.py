@@ -32,23 +32,47 @@ def merge_corres(idx1, idx2):
     return xy1, xy2
 
 
-def fast_reciprocal_NNs(pts1, pts2, S=8, max_iter=10, dtype=np.float64):
+def clear_queries(queries, db, best, second):
+    """True where the arg-max of a query is decided beyond float32 rounding, so that every correct float32 kernel must
+    return the float64 index:  best - second > max(1e-5 |best|, 2 * 24 * 2^-24 * |q| * max_j |d_j|).
+    The first term is the standing rule for unit descriptors; the second is twice the worst-case error of a 24-term
+    float32 dot product (each of best and runner-up can be off by that much) and takes over once rows are not unit
+    length.  best / second are nn_dot's float64 scores."""
+    qn = np.linalg.norm(queries.astype(np.float64), axis=1)
+    dn = np.linalg.norm(db.astype(np.float64), axis=1).max()
+    return (best - second) > np.maximum(1e-5 * np.abs(best), 2 * 24 * 2.0 ** -24 * qn * dn)
+
+
+def fast_reciprocal_NNs(pts1, pts2, S=8, max_iter=10, dtype=np.float64, return_state=False):
+    """return_state=True: the loop's state per seed instead of the merged pairs -- (xy1, xy2, notyet, unclear), where
+    unclear[i] says that seed i met, in some iteration, a query that was not clear (clear_queries): from there on a
+    float32 implementation may legitimately follow another trajectory."""
     H1, W1, D = pts1.shape; H2, W2, _ = pts2.shape
     A = pts1.reshape(-1, D); B = pts2.reshape(-1, D)
     y1, x1 = np.mgrid[S // 2:H1:S, S // 2:W1:S].reshape(2, -1)
     xy1 = np.int32(np.unique(x1 + W1 * y1)); xy2 = np.full_like(xy1, -1)
     old1, old2 = xy1.copy(), xy2.copy()
     notyet = np.ones(len(xy1), bool)
+    unclear = np.zeros(len(xy1), bool)
+
+    def step(src, rows, db):
+        idx, best, second = nn_dot(src[rows], db, dtype=dtype)
+        if return_state:
+            unclear[notyet] |= ~clear_queries(src[rows], db, best, second)
+        return idx
+
     it = 0
     while notyet.any():
-        xy2[notyet] = nn_dot(A[xy1[notyet]], B, dtype=dtype)[0]
+        xy2[notyet] = step(A, xy1[notyet], B)
         notyet &= (old2 != xy2)
-        xy1[notyet] = nn_dot(B[xy2[notyet]], A, dtype=dtype)[0]
+        xy1[notyet] = step(B, xy2[notyet], A)
         notyet &= (old1 != xy1)
         it += 1
         if it >= max_iter:
             break
         old2[:] = xy2; old1[:] = xy1
+    if return_state:
+        return xy1, xy2, notyet, unclear
     conv = ~notyet
     return merge_corres(xy1[conv], xy2[conv])
 

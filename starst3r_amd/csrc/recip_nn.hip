@@ -221,11 +221,9 @@ __global__ __launch_bounds__(256) void k_nn_reduce(int n, int S, const float* __
     }
 }
 
-ST3R_EXPORT int st3r_nn_dot_argmax(st3r_ctx* ctx, void* stream, const float* queries, int n, const float* db,
-                                   int m, int dim, int32_t* nn_out, float* score_out) {
-    ARG_CHECK(ctx && n >= 0 && m > 0 && dim == NN_D && (n == 0 || (queries && nn_out)) && db);
-    if (n == 0) return ST3R_OK;
-    hipStream_t s = (hipStream_t)stream;
+// Segment plan of k_nn_argmax for n queries against m rows: the DB's 32-row tiles are cut into S segments of
+// tiles_per_seg tiles (the last one may be shorter), one wave per (group of 64 queries, segment).
+static void nn_plan(int n, int m, int* S_out, int* tps_out) {
     const int groups = (n + 63) / 64;
     const int tiles = (m + 31) / 32;
     int S = 4096 / groups;           // enough waves to fill 256 CUs a few times over
@@ -233,7 +231,24 @@ ST3R_EXPORT int st3r_nn_dot_argmax(st3r_ctx* ctx, void* stream, const float* que
     if (S > (tiles + 3) / 4) S = (tiles + 3) / 4;  // at least ~4 tiles per segment
     if (S < 1) S = 1;
     const int tiles_per_seg = (tiles + S - 1) / S;
-    S = (tiles + tiles_per_seg - 1) / tiles_per_seg;
+    *tps_out = tiles_per_seg;
+    *S_out = (tiles + tiles_per_seg - 1) / tiles_per_seg;
+}
+
+ST3R_EXPORT int st3r_nn_plan(int n, int m, int* S, int* tiles_per_seg) {
+    ARG_CHECK(n > 0 && m > 0 && S && tiles_per_seg);
+    nn_plan(n, m, S, tiles_per_seg);
+    return ST3R_OK;
+}
+
+ST3R_EXPORT int st3r_nn_dot_argmax(st3r_ctx* ctx, void* stream, const float* queries, int n, const float* db,
+                                   int m, int dim, int32_t* nn_out, float* score_out) {
+    ARG_CHECK(ctx && n >= 0 && m > 0 && dim == NN_D && (n == 0 || (queries && nn_out)) && db);
+    if (n == 0) return ST3R_OK;
+    hipStream_t s = (hipStream_t)stream;
+    const int groups = (n + 63) / 64;
+    int S, tiles_per_seg;
+    nn_plan(n, m, &S, &tiles_per_seg);
     void* p;
     int rc = st3r_arena_get(ctx, SLOT_NN_PART, (sizeof(float) + sizeof(int32_t)) * (size_t)n * S * 2, &p);
     if (rc) return rc;
@@ -323,17 +338,8 @@ ST3R_EXPORT int st3r_recip_nn(st3r_ctx* ctx, void* stream, const float* descA, i
     hipStream_t s = (hipStream_t)stream;
     const int mA = H1 * W1, mB = H2 * W2;
     const int groups = (n + 63) / 64;
-    auto plan = [&](int m, int* S, int* tps) {
-        const int tiles = (m + 31) / 32;
-        int Sx = 4096 / groups;
-        if (Sx < 1) Sx = 1;
-        if (Sx > (tiles + 3) / 4) Sx = (tiles + 3) / 4;
-        if (Sx < 1) Sx = 1;
-        *tps = (tiles + Sx - 1) / Sx;
-        *S = (tiles + *tps - 1) / *tps;
-    };
     int SA, tpsA, SB, tpsB;
-    plan(mA, &SA, &tpsA); plan(mB, &SB, &tpsB);
+    nn_plan(n, mA, &SA, &tpsA); nn_plan(n, mB, &SB, &tpsB);
     const int Smax = SA > SB ? SA : SB;
     void* p;
     int rc = st3r_arena_get(ctx, SLOT_NN_PART, (sizeof(float) + sizeof(int32_t)) * (size_t)n * Smax * 2 +
