@@ -362,13 +362,16 @@ GSO_API void gso_blend_bwd(int C, int W, int H, int tile_size, int tile_w, int t
                            const float* v_alpha, double* v_means2d, double* v_conics, double* v_colors,
                            double* v_opacities) {
     int n_tiles = tile_w * tile_h;
-    (void)n_isects;
     for (int c = 0; c < C; ++c)
         for (int i = 0; i < H; ++i)
             for (int j = 0; j < W; ++j) {
                 int tile_id = (i / tile_size) * tile_w + (j / tile_size);
                 int64_t gt = (int64_t)c * n_tiles + tile_id;
                 int64_t start = offsets[gt];
+                int64_t end = (gt == (int64_t)C * n_tiles - 1) ? n_isects : offsets[gt + 1];
+                /* an empty tile has no batch to walk (gsplat: num_batches == 0); its pixels carry last_ids == 0, which
+                 * for the tiles in front of the first record (start == 0) is the first record of ANOTHER tile */
+                if (end <= start) continue;
                 int64_t p = ((int64_t)c * H + i) * W + j;
                 int64_t bin_final = last_ids[p];
                 float px = (float)j + 0.5f, py = (float)i + 0.5f;
