@@ -257,7 +257,7 @@ static int forward_and_losses(st3r_ctx* ctx, hipStream_t s, const RasterOut& ro,
 // Blend backward of a training step.  The colour backward leaves its stamped (record, tile) slots in *slots (Round 5: the
 // projection backward sums them per pair itself -- no 48-byte per-pair records, no k_gather_vtile launch).
 // need_pairs (depth prior): the colour backward also receives v_alpha, the depth backward writes slots of its own, and
-// both per-pair arrays are materialised by the stand-alone gathers (k_gather_vtile, k_gather_vtile_depth) and added in
+// both per-pair arrays are materialised by the stand-alone gathers (k_gather_vtile<9>, k_gather_vtile<7>) and added in
 // v_pairs -- the kernels and the order of the unfused chain (render_3dgs "RGB+ED" through autograd).
 static int blend_backward(st3r_ctx* ctx, hipStream_t s, const RasterOut& ro, const StepImages& im, bool need_pairs,
                           st3r_vtile_ref* slots, float* v_pairs) {

@@ -55,56 +55,13 @@
 #include "tile_rect.h"
 #include "blend_common.h"
 
-
-
-struct TileGeom {
-    int lb, cam, i, j, start, end, tx0, ty0;
-    bool inside;
-    float px, py;
-};
-
-__device__ __forceinline__ TileGeom tile_geom(int C, int W, int H, int tile_w, int tile_h,
-                                              const int32_t* __restrict__ offsets, int n_isects) {
-    TileGeom g;
-    const int n_tiles = tile_w * tile_h, total = C * n_tiles;
-        g.lb = xcd_remap(blockIdx.x, total, XCD_GROUP(C, n_tiles, tile_w));
-    g.cam = g.lb / n_tiles;
-    const int tile = g.lb - g.cam * n_tiles;
-    const int ty = tile / tile_w, tx = tile - ty * tile_w;
-    g.tx0 = tx * 16; g.ty0 = ty * 16;
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    g.j = g.tx0 + ((w & 1) << 3) + (lane & 7);
-    g.i = g.ty0 + ((w >> 1) << 3) + (lane >> 3);
-    g.inside = (g.i < H) && (g.j < W);
-    g.px = (float)g.j + 0.5f; g.py = (float)g.i + 0.5f;
-    g.start = offsets[g.lb];
-    // n_isects < 0: the offsets array carries one more entry, the total (fused path: the count lives on the device)
-    g.end = (g.lb == total - 1 && n_isects >= 0) ? n_isects : offsets[g.lb + 1];
-    return g;
-}
-
 __device__ __forceinline__ int stage_record(const float4* __restrict__ splats, int64_t id, int t, int tx0, int ty0,
                                             float4* sR) {
     const float4 a = splats[id * 3 + 0];   // x y opacity conic.a
     const float4 b = splats[id * 3 + 1];   // conic.b conic.c r g
     const float4 c = splats[id * 3 + 2];   // b depth radius 0
     stage_qform(a, b, c, t, sR);
-    // A quadrant (8x8 pixel centres) is relevant iff the ellipse {sigma(p) <= tau}, tau = ln(255 opacity), reaches
-    // it: either the mean lies inside, or the minimum of sigma over one of its four edges is <= tau (sigma is
-    // convex, so the minimum over the square sits on the boundary when the mean is outside).  tau is inflated
-    // (2e-4 relative + 2e-4) so that every pixel of a quadrant declared irrelevant fails the alpha test of the
-    // blend loop in float arithmetic as well.  Costs ~150 instructions per RECORD (one lane), and removes a
-    // quarter of the per-(record, quadrant) wave iterations of the axis-aligned-box test it replaces.
-    EllipseTest et;
-    if (!ellipse_prepare(a.z, a.w, b.x, b.y, &et)) return 0;
-    const float rx = ((float)tx0 + 0.5f) - a.x, ry = ((float)ty0 + 0.5f) - a.y;  // first pixel centre - mean
-    int rel = 0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const float dx0 = rx + (float)((q & 1) * 8), dy0 = ry + (float)((q >> 1) * 8);
-        rel |= ellipse_hits_square(et, dx0, dx0 + 7.0f, dy0, dy0 + 7.0f) ? (1 << q) : 0;
-    }
-    return rel;
+    return quadrant_relevance(a, b, tx0, ty0);
 }
 
 // TRAIN (the fused training calls): the per-trip bookkeeping of a saturating pixel -- threshold, alpha, T and index
@@ -223,28 +180,15 @@ __global__ __launch_bounds__(BLK) void k_blend_fwd(int C, int W, int H, int tile
     if (tile_nb && threadIdx.x == 0) tile_nb[g.lb] = nb;
 }
 
-// scratch for the forward->backward hand-off lives in the ctx
-static int hand_off_buffers(st3r_ctx* ctx, int C, int tile_w, int tile_h, int64_t n_isects, uint64_t** cmask,
-                            int64_t* words, int32_t** tile_nb) {
-    const int64_t total = (int64_t)C * tile_w * tile_h;
-    *words = (n_isects >> 6) + 4 * total + 8;
-    ARENA_GET(SLOT_CMASK, uint64_t, 4 * (size_t)*words, cm);
-    ARENA_GET(SLOT_TILE_NB, int32_t, total, nb);
-    *cmask = cm; *tile_nb = nb;
-    return ST3R_OK;
-}
-
 int st3r_blend_fwd_impl(st3r_ctx* ctx, hipStream_t s, const RasterOut& ro, float* rgb, float* alpha, int32_t* last_ids,
                         bool for_backward, bool end_in_offsets) {
     const int C = ro.C, W = ro.W, H = ro.H, tile_w = ro.tile_w, tile_h = ro.tile_h;
     const int total = C * tile_w * tile_h;
     uint64_t* cmask = nullptr; int64_t words = 0; int32_t* tile_nb = nullptr;
     if (for_backward) {
-        int rc = hand_off_buffers(ctx, C, tile_w, tile_h, ro.n_isects, &cmask, &words, &tile_nb);
+        int rc = hand_off_buffers(ctx, total, ro.n_isects, true, &cmask, &words, &tile_nb);   // (scratch of the ctx)
         if (rc) return rc;
     }
-    // the fused training calls (their own backward follows) take the TRAIN variant; debug flag 128 keeps them on the
-    // gsplat-style bookkeeping (A/B)
     // the fused training calls blend with cell lists (gs_blend_cells.hip; debug flag 128 keeps them on the quadrant
     // kernel, flag 512 sends st3r_gs_render through the cell kernel as well: A/B and tests)
     if ((for_backward && end_in_offsets && !(ctx->debug_flags & 128)) || (end_in_offsets && (ctx->debug_flags & 512)))
@@ -264,10 +208,9 @@ ST3R_EXPORT int st3r_gs_blend_fwd(st3r_ctx* ctx, void* stream, int C, int width,
                                   int tile_w, int tile_h, const float* splats, const int32_t* offsets,
                                   const int32_t* flatten_ids, int64_t n_isects, float* rgb, float* alpha,
                                   int32_t* last_ids) {
-    ARG_CHECK(ctx && C > 0 && width > 0 && height > 0 && tile_size == 16);
-    ARG_CHECK(tile_w == (width + 15) / 16 && tile_h == (height + 15) / 16);
-    ARG_CHECK(splats && offsets && rgb && alpha && last_ids && n_isects >= 0 && n_isects < 2147483647LL);
-    ARG_CHECK(n_isects == 0 || flatten_ids);
+    if (int rc = check_blend_args(ctx, C, width, height, tile_size, tile_w, tile_h, splats, offsets, flatten_ids, n_isects))
+        return rc;
+    ARG_CHECK(rgb && alpha && last_ids);
     return st3r_blend_fwd_impl(ctx, (hipStream_t)stream,
                                stage_lists(C, width, height, tile_w, tile_h, splats, offsets, flatten_ids, n_isects), rgb,
                                alpha, last_ids, true, false);
@@ -295,10 +238,7 @@ __device__ __forceinline__ void bwd_phase2(const float2* __restrict__ pr, unsign
     const float2 mean = *reinterpret_cast<const float2*>(&sA[t]);
     const float dy = mean.y - qyf_lane;
     const float2* src = pr + r * PAIR_STRIDE + PAIR_AT(part * CHUNK);
-    // The lane's pixels are i = 0 .. CHUNK-1 to the right of its first one: with d0 = dx of the first pixel,
-    // sum g dx = d0 W0 - W1 and sum g dx^2 = d0 (d0 W0 - 2 W1) + W2 for the index moments W_k = sum i^k g_i -- 12 VALU
-    // instead of 21 for CHUNK = 4 (k_blend_bwd 2.27 -> 2.17 ms); the offsets are at most CHUNK-1 pixels, so the
-    // cancellation costs a few ulps.
+    // index moments W_k = sum i^k g_i over the lane's pixels (i = 0 .. CHUNK-1 to the right of its first one): see run_sums
     float W0 = 0.f, W1 = 0.f, W2 = 0.f, Sr = 0.f, Sg = 0.f, Sb = 0.f;
 #pragma unroll
     for (int i = 0; i < CHUNK; ++i) {
@@ -308,11 +248,9 @@ __device__ __forceinline__ void bwd_phase2(const float2* __restrict__ pr, unsign
         if (i > 1) { W1 = fmaf((float)i, v.x, W1); W2 = fmaf((float)(i * i), v.x, W2); }
         Sr = fmaf(v.y, pvr[i], Sr); Sg = fmaf(v.y, pvg[i], Sg); Sb = fmaf(v.y, pvb[i], Sb);
     }
-    const float d0 = mean.x - qxf_lane;
-    const float So = W0, Sx = fmaf(d0, W0, -W1), Sxx = fmaf(d0, Sx - W1, W2);
-    const float Sy = So * dy, Sxy = Sx * dy, Syy = Sy * dy;  // dy is the same for the lane's pixels
+    const RunSums m = run_sums(W0, W1, W2, mean.x - qxf_lane, dy);
     float k0, k1, k2;
-    reduce9_rows(Sx, Sy, So, Sxx, Sxy, Syy, Sr, Sg, Sb, k0, k1, k2);
+    reduce9_rows(m.Sx, m.Sy, m.So, m.Sxx, m.Sxy, m.Syy, Sr, Sg, Sb, k0, k1, k2);
     if (r < cnt && (lane & 3) == 0) {
         // bank b of the record's row -> slots: k0 -> {0,2,1,3}[b], k1 -> {4,6,5,7}[b], k2 -> 8 (bank 0)
         const int b = (lane >> 2) & 3;
@@ -445,9 +383,7 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(8))) void k
                 // (scenes of many slots per pair: the pair is marked as touched by this backward call -- the gather skips
                 // the slot ranges of pairs nobody marked; a benign race, every writer stores the same stamp)
                 if (TOUCH) reinterpret_cast<uint32_t*>(const_cast<uint64_t*>(rects))[my_id] = (uint32_t)stamp;
-                const uint64_t r = rectbase[my_id];
-                const int x0 = (int)(r & 0x3FF), y0 = (int)((r >> 10) & 0x3FF), rw = (int)((r >> 20) & 0x3FF);
-                my_u = (int)(r >> 32) + ((g.ty0 >> 4) - y0) * rw + ((g.tx0 >> 4) - x0);
+                my_u = slot_of_rectbase(rectbase[my_id], g.tx0, g.ty0);
                 my_op = a.z; my_ca = a.w; my_cbb = b.x; my_cc = b.y;
             } else if (my_cb) {
                 int x0, y0, rw;
@@ -461,7 +397,7 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(8))) void k
                     x0 = tr.x0; y0 = tr.y0; rw = tr.x1 - tr.x0;
                 }
                 const int cum_excl = my_id == 0 ? 0 : cum[my_id - 1];
-                my_u = cum_excl + ((g.ty0 >> 4) - y0) * rw + ((g.tx0 >> 4) - x0);
+                my_u = slot_of_rect(cum_excl, x0, y0, rw, g.tx0, g.ty0);
                 my_op = a.z; my_ca = a.w; my_cbb = b.x; my_cc = b.y;
             }
         }
@@ -564,61 +500,6 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(8))) void k
     }
 }
 
-// v_splats[pid] = sum over the pair's tiles of the slots stamped by this backward call, in slot order (deterministic
-// given the slots).  A workgroup owns 256 consecutive (camera, gaussian) pairs, whose slots are one contiguous range.
-// The range is streamed through LDS 256 slots at a time with lane = slot (coalesced reads, no per-lane trip counts on
-// the HBM side; the next 256 slots are in flight while the current ones are summed); then lane = pair adds the rows
-// of its own slots in slot order.  Measured at SYNTH-1M: 0.26 ms, one thread per pair walking its slots 0.35 ms.
-__global__ __launch_bounds__(256) void k_gather_vtile(int64_t n_pairs, const int32_t* __restrict__ cum,
-                                                      const float* __restrict__ vtile, int stamp, unsigned vt_cap,
-                                                      float4* __restrict__ v_splats) {
-    constexpr int ROW = ACC_VALS;   // odd stride: rows of neighbouring slots fall into different banks
-    __shared__ int sCum[257];
-    __shared__ float sVal[256 * ROW];
-    const int tid = threadIdx.x;
-    const int64_t p0 = (int64_t)blockIdx.x * 256;
-    const int np = (int)min((int64_t)256, n_pairs - p0);
-    if (tid == 0) sCum[0] = p0 == 0 ? 0 : cum[p0 - 1];
-    sCum[tid + 1] = cum[p0 + min(tid, np - 1)];
-    __syncthreads();
-    const int s0 = sCum[0], s1 = sCum[np];
-    const int my_start = sCum[tid], my_end = tid < np ? sCum[tid + 1] : sCum[tid];
-    float acc[ACC_VALS];
-#pragma unroll
-    for (int k = 0; k < ACC_VALS; ++k) acc[k] = 0.f;
-    float2 q0, q1, q2, q3, q4;
-    auto fetch = [&](int u) {
-        q0 = q1 = q2 = q3 = q4 = make_float2(0.f, 0.f);   // stamp 0 = never written
-        if (u < s1 && (unsigned)u < vt_cap) {   // (vt_cap: see the flush of k_blend_bwd)
-            const float2* src = reinterpret_cast<const float2*>(vtile + (int64_t)u * VT_STRIDE);
-            q0 = src[0]; q1 = src[1]; q2 = src[2]; q3 = src[3]; q4 = src[4];
-        }
-    };
-    fetch(s0 + tid);
-    for (int base = s0; base < s1; base += 256) {
-        const bool live = __float_as_int(q4.y) == stamp;
-        float* row = sVal + tid * ROW;
-        row[0] = live ? q0.x : 0.f; row[1] = live ? q0.y : 0.f; row[2] = live ? q1.x : 0.f;
-        row[3] = live ? q1.y : 0.f; row[4] = live ? q2.x : 0.f; row[5] = live ? q2.y : 0.f;
-        row[6] = live ? q3.x : 0.f; row[7] = live ? q3.y : 0.f; row[8] = live ? q4.x : 0.f;
-        __syncthreads();
-        fetch(base + 256 + tid);
-        const int lo = max(my_start, base) - base, hi = min(my_end, base + 256) - base;
-        for (int r = lo; r < hi; ++r) {
-            const float* src = sVal + r * ROW;
-#pragma unroll
-            for (int k = 0; k < ACC_VALS; ++k) acc[k] += src[k];
-        }
-        __syncthreads();
-    }
-    if (tid < np) {
-        const int64_t pid = p0 + tid;
-        v_splats[pid * 3 + 0] = make_float4(acc[0], acc[1], acc[2], acc[3]);
-        v_splats[pid * 3 + 1] = make_float4(acc[4], acc[5], acc[6], acc[7]);
-        v_splats[pid * 3 + 2] = make_float4(acc[8], 0.f, 0.f, 0.f);
-    }
-}
-
 int st3r_blend_bwd_impl(st3r_ctx* ctx, hipStream_t s, const RasterOut& ro, const float* alpha, const int32_t* last_ids,
                         const float* v_rgb, const float* v_alpha, float* v_splats, bool end_in_offsets,
                         st3r_vtile_ref* defer) {
@@ -631,16 +512,14 @@ int st3r_blend_bwd_impl(st3r_ctx* ctx, hipStream_t s, const RasterOut& ro, const
         if (!defer) HIP_TRY(hipMemsetAsync(v_splats, 0, sizeof(float) * ST3R_SPLAT_STRIDE * (size_t)n_pairs, s));
         return ST3R_OK;   // (defer: every pair's slot range is empty -- `cum` is all zeros -- and vt_cap = 0 guards the rest)
     }
+    const int total = C * tile_w * tile_h;
     uint64_t* cmask; int64_t words; int32_t* tile_nb;
-    int rc = hand_off_buffers(ctx, C, tile_w, tile_h, n_isects, &cmask, &words, &tile_nb);
+    int rc = hand_off_buffers(ctx, total, n_isects, true, &cmask, &words, &tile_nb);
     if (rc) return rc;
-    // per-(record, tile) partial gradients: 9 floats + a stamp; a slot counts only if its stamp equals this
-    // call's, so the buffer is never cleared per call (the stamps are zeroed when the buffer is (re)allocated and
-    // when the counter is about to wrap)
-    void* p; int grown = 0;
-    rc = st3r_arena_get2(ctx, SLOT_VTILE, sizeof(float) * VT_STRIDE * (size_t)n_isects, &p, &grown);
+    // the slots: 9 sums + the stamp (stamped_slots)
+    StampedSlots sl;
+    rc = stamped_slots(ctx, s, SLOT_VTILE, VT_STRIDE, n_isects, &ctx->bwd_stamp, &sl);
     if (rc) return rc;
-    float* vtile = (float*)p;
     // Per-pair "touched" stamps, only where they pay: a scene with many slots per pair (large Gaussians; more than eight
     // per pair SLOT of the call -- the gather's item-parallel form, which is the one that skips, starts at six per visible pair
     // of a wave, and SYNTH-1M late in training reaches five) AND a gather that follows in the projection backward.  There most slots belong to pairs that never contribute
@@ -654,34 +533,21 @@ int st3r_blend_bwd_impl(st3r_ctx* ctx, hipStream_t s, const RasterOut& ro, const
         if (rc) return rc;
         touch = (uint32_t*)pt;
     }
-    if (grown || ctx->bwd_stamp >= 2147483000) {   // (the stamps restart: both stamp stores are cleared together)
-        HIP_TRY(hipMemsetAsync(p, 0, ctx->slot_bytes[SLOT_VTILE], s));
+    if (sl.restarted) {   // (the stamps restart -- the slots grew or the counter was about to wrap: both stamp stores are cleared together)
         if (ctx->slot_ptr[SLOT_PAIR_TOUCH])
             HIP_TRY(hipMemsetAsync(ctx->slot_ptr[SLOT_PAIR_TOUCH], 0, ctx->slot_bytes[SLOT_PAIR_TOUCH], s));
-        ctx->bwd_stamp = 0;
     } else if (grown_t) {   // (a fresh touch array: zeros are older than every stamp in use)
         HIP_TRY(hipMemsetAsync(touch, 0, ctx->slot_bytes[SLOT_PAIR_TOUCH], s));
     }
-    const int stamp = ++ctx->bwd_stamp;
-    const int total = C * tile_w * tile_h;
-    const unsigned vt_cap = (unsigned)(ctx->slot_bytes[SLOT_VTILE] / (sizeof(float) * VT_STRIDE));
-    if (v_alpha)
-        hipLaunchKernelGGL(k_blend_bwd<true>, dim3(total), dim3(BLK), 0, s, C, W, H, tile_w, tile_h,
-                           (const float4*)ro.splats, ro.offsets, ro.flat, end_in_offsets ? -1 : (int)n_isects, alpha, last_ids, v_rgb,
-                           v_alpha, cmask, words, tile_nb, cum, rects, rectbase, tight, vtile, stamp, vt_cap);
-    else if (touch)
-        hipLaunchKernelGGL((k_blend_bwd<false, true>), dim3(total), dim3(BLK), 0, s, C, W, H, tile_w, tile_h,
-                           (const float4*)ro.splats, ro.offsets, ro.flat, end_in_offsets ? -1 : (int)n_isects, alpha, last_ids, v_rgb,
-                           v_alpha, cmask, words, tile_nb, cum, reinterpret_cast<const uint64_t*>(touch), rectbase, tight, vtile,
-                           stamp, vt_cap);
-    else
-        hipLaunchKernelGGL(k_blend_bwd<false>, dim3(total), dim3(BLK), 0, s, C, W, H, tile_w, tile_h,
-                           (const float4*)ro.splats, ro.offsets, ro.flat, end_in_offsets ? -1 : (int)n_isects, alpha, last_ids, v_rgb,
-                           v_alpha, cmask, words, tile_nb, cum, rects, rectbase, tight, vtile, stamp, vt_cap);
+    // TOUCH takes the touch stamps in the place of the rectangles it does not read (see k_blend_bwd)
+    const auto kernel = v_alpha ? k_blend_bwd<true> : touch ? k_blend_bwd<false, true> : k_blend_bwd<false>;
+    hipLaunchKernelGGL(kernel, dim3(total), dim3(BLK), 0, s, C, W, H, tile_w, tile_h, (const float4*)ro.splats, ro.offsets,
+                       ro.flat, end_in_offsets ? -1 : (int)n_isects, alpha, last_ids, v_rgb, v_alpha, cmask, words, tile_nb, cum,
+                       touch ? reinterpret_cast<const uint64_t*>(touch) : rects, rectbase, tight, sl.vtile, sl.stamp, sl.cap);
     LAUNCH_CHECK();
-    if (defer) { *defer = st3r_vtile_ref{cum, vtile, stamp, vt_cap, touch}; return ST3R_OK; }
-    hipLaunchKernelGGL(k_gather_vtile, dim3(ceil_div(n_pairs, 256)), dim3(256), 0, s, n_pairs, cum, vtile, stamp, vt_cap,
-                       (float4*)v_splats);
+    if (defer) { *defer = st3r_vtile_ref{cum, sl.vtile, sl.stamp, sl.cap, touch}; return ST3R_OK; }
+    hipLaunchKernelGGL(k_gather_vtile<ACC_VALS>, dim3(ceil_div(n_pairs, 256)), dim3(256), 0, s, n_pairs, cum, sl.vtile,
+                       sl.stamp, sl.cap, (float4*)v_splats);
     LAUNCH_CHECK();
     return ST3R_OK;
 }
@@ -691,8 +557,8 @@ int st3r_blend_bwd_impl(st3r_ctx* ctx, hipStream_t s, const RasterOut& ro, const
 // stand-alone st3r_gs_blend_bwd.
 int st3r_gather_vtile_impl(hipStream_t s, int64_t n_pairs, const st3r_vtile_ref* slots, float* v_splats) {
     if (n_pairs <= 0) return ST3R_OK;
-    hipLaunchKernelGGL(k_gather_vtile, dim3(ceil_div(n_pairs, 256)), dim3(256), 0, s, n_pairs, slots->cum, slots->vtile,
-                       slots->stamp, slots->vt_cap, (float4*)v_splats);
+    hipLaunchKernelGGL(k_gather_vtile<ACC_VALS>, dim3(ceil_div(n_pairs, 256)), dim3(256), 0, s, n_pairs, slots->cum,
+                       slots->vtile, slots->stamp, slots->vt_cap, (float4*)v_splats);
     LAUNCH_CHECK();
     return ST3R_OK;
 }
@@ -702,10 +568,9 @@ ST3R_EXPORT int st3r_gs_blend_bwd(st3r_ctx* ctx, void* stream, int C, int width,
                                   const int32_t* flatten_ids, int64_t n_isects, const float* alpha,
                                   const int32_t* last_ids, const float* v_rgb, const float* v_alpha,
                                   const int32_t* cum_tiles, int64_t n_pairs, float* v_splats) {
-    ARG_CHECK(ctx && C > 0 && width > 0 && height > 0 && tile_size == 16);
-    ARG_CHECK(tile_w == (width + 15) / 16 && tile_h == (height + 15) / 16);
-    ARG_CHECK(splats && offsets && alpha && last_ids && v_rgb && v_splats && cum_tiles && n_pairs >= 0);
-    ARG_CHECK(n_isects >= 0 && n_isects < 2147483647LL && (n_isects == 0 || flatten_ids));
+    if (int rc = check_blend_args(ctx, C, width, height, tile_size, tile_w, tile_h, splats, offsets, flatten_ids, n_isects))
+        return rc;
+    ARG_CHECK(alpha && last_ids && v_rgb && v_splats && cum_tiles && n_pairs >= 0);
     return st3r_blend_bwd_impl(ctx, (hipStream_t)stream,
                                stage_lists(C, width, height, tile_w, tile_h, splats, offsets, flatten_ids, n_isects, cum_tiles,
                                            n_pairs),

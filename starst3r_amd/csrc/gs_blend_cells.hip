@@ -138,6 +138,7 @@ struct CellTile {
 // quadrant, lane idx of the row the pixel (idx & 3, idx >> 2) of the cell
 __device__ __forceinline__ CellTile cell_tile(int C, int W, int H, int tile_w, int tile_h, const int32_t* __restrict__ offsets) {
     CellTile g;
+    // (the tile part mirrors tile_geom of blend_common.h; a shared helper changed the code of k_blend_fwd)
     const int n_tiles = tile_w * tile_h, total = C * n_tiles;
     g.lb = xcd_remap(blockIdx.x, total, XCD_GROUP(C, n_tiles, tile_w));
     g.cam = g.lb / n_tiles;

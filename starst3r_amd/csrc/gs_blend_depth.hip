@@ -11,56 +11,29 @@
 // that saturated the pixel (not blended).  T and alpha T are formed by the same two multiplications, so D equals, bit for
 // bit, channel 0 of a colour render whose colours were overwritten with (z, 0, 0).
 //
-// Mapping: as gs_blend.hip.  One workgroup = one 16x16 tile = 4 wave64, wave w owns the 8x8 quadrant (w&1, w>>1), tiles
-// handed to the XCDs through xcd_remap.  The forward stages 256 records per batch, 32 bytes each (x y opacity qa | qb qc z
-// -: no colour), tests each against the four quadrants (ellipse_hits_square) and walks the set bits only.
+// Mapping: as gs_blend.hip, through the same functions of blend_common.h -- tile_geom (one workgroup = one 16x16 tile,
+// wave w owns the 8x8 quadrant (w&1, w>>1), tiles handed to the XCDs through xcd_remap) and quadrant_relevance.  The forward
+// stages 256 records per batch, 32 bytes each (x y opacity qa | qb qc z -: no colour), and walks the set bits only.
 //
 // Backward: k_blend_bwd's two-phase transposition with one channel whose "colour" is z_i,
 //     dL/dalpha_i = (T_i z_i - S_i / (1 - alpha_i)) v_D,     S_i = depth accumulated behind record i
 // (no background, no v_alpha term).  Phase 1 (lanes = pixels) leaves (alpha dL/dalpha, alpha T) per (record, pixel) in a
 // wave-private LDS buffer; phase 2 (lanes = records x pixel runs) accumulates the seven sums
 //     sum g {1, dx, dy, dx^2, dx dy, dy^2}  and  sum (alpha T) v_D
-// and meets them in DPP row reductions (reduce9_rows with two idle inputs: a first version, the reduction is not tuned for
-// seven values).  Per-(record, tile) results go to stamped 32-byte slots of their own (7 sums + stamp, four 8-byte stores)
-// and k_gather_vtile_depth adds a pair's slots in slot order: no atomics, fixed summation order, same inputs -> same bits.
-// It walks the contribution masks the colour forward left in the ctx, like st3r_gs_blend_bwd.
+// (run_sums) and meets them in DPP row reductions (reduce9_rows with two idle inputs: a first version, the reduction is not
+// tuned for seven values).  Per-(record, tile) results go to stamped 32-byte slots of their own (DVT_STRIDE: 7 sums + stamp;
+// slot_of_rectbase / slot_of_rect, stamped_slots) and k_gather_vtile<DACC_VALS> adds a pair's slots in slot order: no
+// atomics, fixed summation order, same inputs -> same bits.  It walks the contribution masks the colour forward left in
+// the ctx (hand_off_buffers), like st3r_gs_blend_bwd.  What k_blend_depth_bwd still repeats of k_blend_bwd -- that kernel's
+// register allocation does not survive the move into a shared function -- is marked `mirrors k_blend_bwd`.
 #include <type_traits>
 
 #include "stages.h"
 #include "tile_rect.h"
 #include "blend_common.h"
 
-#define DACC_VALS 7     // S_x S_y S_o S_xx S_xy S_yy S_z per staged record and wave
-#define DVT_STRIDE 8    // per-(record, tile) slot: 7 partial gradients + the stamp = 4 x 8 B
-
-struct DepthTile {
-    int lb, cam, i, j, start, end, tx0, ty0;
-    bool inside;
-    float px, py;
-};
-
-__device__ __forceinline__ DepthTile depth_tile_geom(int C, int W, int H, int tile_w, int tile_h,
-                                                     const int32_t* __restrict__ offsets, int n_isects) {
-    DepthTile g;
-    const int n_tiles = tile_w * tile_h, total = C * n_tiles;
-    g.lb = xcd_remap(blockIdx.x, total, XCD_GROUP(C, n_tiles, tile_w));
-    g.cam = g.lb / n_tiles;
-    const int tile = g.lb - g.cam * n_tiles;
-    const int ty = tile / tile_w, tx = tile - ty * tile_w;
-    g.tx0 = tx * 16; g.ty0 = ty * 16;
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    g.j = g.tx0 + ((w & 1) << 3) + (lane & 7);
-    g.i = g.ty0 + ((w >> 1) << 3) + (lane >> 3);
-    g.inside = (g.i < H) && (g.j < W);
-    g.px = (float)g.j + 0.5f; g.py = (float)g.i + 0.5f;
-    g.start = offsets[g.lb];
-    // n_isects < 0 (fused step): the table carries the record total as its last entry, as for the colour kernels
-    g.end = (n_isects >= 0 && g.lb == total - 1) ? n_isects : offsets[g.lb + 1];
-    return g;
-}
-
 // q-form of record `id` in LDS slot t, two words: (x y opacity qa | qb qc z -) with qa, qb, qc formed exactly as
-// stage_qform forms them; returns the 4-bit quadrant relevance (see stage_record of gs_blend.hip)
+// stage_qform forms them; returns the 4-bit quadrant relevance
 __device__ __forceinline__ int stage_record_depth(const float4* __restrict__ splats, int64_t id, int t, int tx0, int ty0,
                                                   float4* sR) {
     const float4 a = splats[id * 3 + 0];   // x y opacity conic.a
@@ -68,16 +41,7 @@ __device__ __forceinline__ int stage_record_depth(const float4* __restrict__ spl
     const float z = reinterpret_cast<const float*>(splats)[id * 12 + 9];
     sR[2 * t + 0] = make_float4(a.x, a.y, a.z, -0.5f * LOG2E * a.w);
     sR[2 * t + 1] = make_float4(-LOG2E * b.x, -0.5f * LOG2E * b.y, z, 0.f);
-    EllipseTest et;
-    if (!ellipse_prepare(a.z, a.w, b.x, b.y, &et)) return 0;
-    const float rx = ((float)tx0 + 0.5f) - a.x, ry = ((float)ty0 + 0.5f) - a.y;  // first pixel centre - mean
-    int rel = 0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const float dx0 = rx + (float)((q & 1) * 8), dy0 = ry + (float)((q >> 1) * 8);
-        rel |= ellipse_hits_square(et, dx0, dx0 + 7.0f, dy0, dy0 + 7.0f) ? (1 << q) : 0;
-    }
-    return rel;
+    return quadrant_relevance(a, b, tx0, ty0);
 }
 
 __global__ __launch_bounds__(BLK) void k_blend_depth_fwd(int C, int W, int H, int tile_w, int tile_h,
@@ -88,7 +52,7 @@ __global__ __launch_bounds__(BLK) void k_blend_depth_fwd(int C, int W, int H, in
                                                          float* __restrict__ out_depth) {
     __shared__ float4 sR[BLK * 2];
     __shared__ uint64_t sMask[4][4];  // [quadrant][64-record chunk]
-    const DepthTile g = depth_tile_geom(C, W, H, tile_w, tile_h, offsets, n_isects);
+    const TileGeom g = tile_geom(C, W, H, tile_w, tile_h, offsets, n_isects);
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int64_t p = ((int64_t)g.cam * H + g.i) * W + g.j;
     // index of the last record the colour forward blended into this pixel (0 for a pixel nothing reached: record 0 then
@@ -131,21 +95,6 @@ __global__ __launch_bounds__(BLK) void k_blend_depth_fwd(int C, int W, int H, in
     if (g.inside) out_depth[p] = d;
 }
 
-// the contribution masks and batch counts st3r_gs_blend_fwd left in the ctx (layout: hand_off_buffers of gs_blend.hip)
-static int forward_hand_off(st3r_ctx* ctx, int C, int tile_w, int tile_h, int64_t n_isects, const uint64_t** cmask,
-                            int64_t* words, const int32_t** tile_nb) {
-    const int64_t total = (int64_t)C * tile_w * tile_h;
-    *words = (n_isects >> 6) + 4 * total + 8;
-    if (!ctx->slot_ptr[SLOT_CMASK] || ctx->slot_bytes[SLOT_CMASK] < sizeof(uint64_t) * 4 * (size_t)*words ||
-        !ctx->slot_ptr[SLOT_TILE_NB] || ctx->slot_bytes[SLOT_TILE_NB] < sizeof(int32_t) * (size_t)total) {
-        st3r_set_error("st3r_gs_blend_depth_bwd must follow st3r_gs_blend_fwd of the same lists on the same ctx");
-        return ST3R_ERR_INVALID;
-    }
-    *cmask = (const uint64_t*)ctx->slot_ptr[SLOT_CMASK];
-    *tile_nb = (const int32_t*)ctx->slot_ptr[SLOT_TILE_NB];
-    return ST3R_OK;
-}
-
 int st3r_blend_depth_fwd_impl(st3r_ctx* ctx, hipStream_t s, const RasterOut& ro, const int32_t* last_ids, float* depth,
                               bool end_in_offsets) {
     (void)ctx;
@@ -160,10 +109,9 @@ ST3R_EXPORT int st3r_gs_blend_depth_fwd(st3r_ctx* ctx, void* stream, int C, int 
                                         int tile_w, int tile_h, const float* splats, const int32_t* offsets,
                                         const int32_t* flatten_ids, int64_t n_isects, const float* alpha,
                                         const int32_t* last_ids, float* depth) {
-    ARG_CHECK(ctx && C > 0 && width > 0 && height > 0 && tile_size == 16);
-    ARG_CHECK(tile_w == (width + 15) / 16 && tile_h == (height + 15) / 16);
-    ARG_CHECK(splats && offsets && alpha && last_ids && depth && n_isects >= 0 && n_isects < 2147483647LL);
-    ARG_CHECK(n_isects == 0 || flatten_ids);
+    if (int rc = check_blend_args(ctx, C, width, height, tile_size, tile_w, tile_h, splats, offsets, flatten_ids, n_isects))
+        return rc;
+    ARG_CHECK(alpha && last_ids && depth);
     (void)alpha;   // (part of the colour render's result the call is bound to; T is rebuilt from the records)
     return st3r_blend_depth_fwd_impl(ctx, (hipStream_t)stream,
                                      stage_lists(C, width, height, tile_w, tile_h, splats, offsets, flatten_ids, n_isects),
@@ -194,11 +142,9 @@ __device__ __forceinline__ void depth_bwd_phase2(const float2* __restrict__ pr, 
         if (i > 1) { W1 = fmaf((float)i, v.x, W1); W2 = fmaf((float)(i * i), v.x, W2); }
         Sz = fmaf(v.y, pvd[i], Sz);
     }
-    const float d0 = mean.x - qxf_lane;
-    const float So = W0, Sx = fmaf(d0, W0, -W1), Sxx = fmaf(d0, Sx - W1, W2);
-    const float Sy = So * dy, Sxy = Sx * dy, Syy = Sy * dy;  // dy is the same for the lane's pixels
+    const RunSums m = run_sums(W0, W1, W2, mean.x - qxf_lane, dy);
     float k0, k1, k2;
-    reduce9_rows(Sx, Sy, So, Sxx, Sxy, Syy, Sz, 0.f, 0.f, k0, k1, k2);
+    reduce9_rows(m.Sx, m.Sy, m.So, m.Sxx, m.Sxy, m.Syy, Sz, 0.f, 0.f, k0, k1, k2);
     (void)k2;
     if (r < cnt && (lane & 3) == 0) {
         // bank b of the record's row -> slots: k0 -> {0,2,1,3}[b], k1 -> {4,6,5,-}[b]
@@ -222,7 +168,7 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(8))) void k
     __shared__ float sAccW[4][HB * DACC_VALS];            // per wave: the sums of the records it met this round
     __shared__ float2 sPair[4][CHUNK * PAIR_STRIDE];      // per wave: (g, fac) of CHUNK records x 64 pixels
     __shared__ uint64_t sClampW;                          // staged records that need the full tests (`hard` below)
-    const DepthTile g = depth_tile_geom(C, W, H, tile_w, tile_h, offsets, n_isects);
+    const TileGeom g = tile_geom(C, W, H, tile_w, tile_h, offsets, n_isects);
     const int nb = tile_nb[g.lb];
     if (nb == 0) return;
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -279,24 +225,22 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(8))) void k
                 sA[t] = make_float4(a.x, a.y, a.z, -0.5f * LOG2E * a.w);
                 sB[t] = make_float4(-LOG2E * b.x, -0.5f * LOG2E * b.y, c.y, 0.f);
             }
-            // records that can neither reach the 0.999 clamp nor fail the sigma >= 0 test (see k_blend_bwd)
+            // mirrors k_blend_bwd: the `hard` record test (records that can reach the 0.999 clamp or fail the sigma >= 0 test)
             const float det_ = a.w * b.y - b.x * b.x;
             const bool hard = my_cb && !(a.z <= 0.998f && a.w > 0.f && b.y > 0.f && det_ >= 2e-3f * (a.w * b.y));
             const uint64_t cw = __builtin_amdgcn_ballot_w64(hard);
             if (t == 0) sClampW = cw;
             if (my_cb) {
-                // slot = cum_excl[pid] + index of this tile inside the record's tile rectangle (the emit kernel's integers)
                 // (fused step: `cum` scans the TIGHT rectangles the emission used -- slot base and rectangle arrive in one
-                // word per pair, or the rectangle is rebuilt as k_blend_bwd rebuilds it)
+                // word per pair)
                 if (rectbase) {
-                    const uint64_t r = rectbase[my_id];
-                    const int x0 = (int)(r & 0x3FF), y0 = (int)((r >> 10) & 0x3FF), rw = (int)((r >> 20) & 0x3FF);
-                    my_u = (int)(r >> 32) + ((g.ty0 >> 4) - y0) * rw + ((g.tx0 >> 4) - x0);
+                    my_u = slot_of_rectbase(rectbase[my_id], g.tx0, g.ty0);
                 } else {
+                    // mirrors k_blend_bwd: the rectangle rebuilt from the record
                     TileRect tr = ref_tile_rect(a.x, a.y, (float)__float_as_int(c.z), 16, tile_w, tile_h);
                     if (tight) tr = tight_tile_rect(tr, a.x, a.y, a.z, a.w, b.x, b.y);
                     const int cum_excl = my_id == 0 ? 0 : cum[my_id - 1];
-                    my_u = cum_excl + ((g.ty0 >> 4) - tr.y0) * (tr.x1 - tr.x0) + ((g.tx0 >> 4) - tr.x0);
+                    my_u = slot_of_rect(cum_excl, tr.x0, tr.y0, tr.x1 - tr.x0, g.tx0, g.ty0);
                 }
                 my_op = a.z; my_ca = a.w; my_cbb = b.x; my_cc = b.y;
             }
@@ -321,6 +265,7 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(8))) void k
                         const float P = blend_power(dx, dy, a.w, q.x, q.y);
                         const float vis0 = __builtin_amdgcn_exp2f(P);
                         const float ov0 = a.z * vis0;
+                        // mirrors k_blend_bwd: the phase-1 alpha test, CLAMP / easy-round forms (here always with the index bound)
                         float alpha;
                         if (CLAMP) {
                             const float al0 = fminf(0.999f, ov0);
@@ -372,6 +317,7 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(8))) void k
                     for (int k = 0; k < DACC_VALS; ++k) acc[k] += sAccW[ww][threadIdx.x * DACC_VALS + k];
                 }
             }
+            // mirrors k_blend_bwd: the flush's geometric part (six sums and the record constants -> three 8-byte words)
             // v_sigma = -opacity g_o;  v_mean2d = v_sigma (a dx + b dy, b dx + c dy);  v_conic = v_sigma (dx^2/2, dx dy, dy^2/2)
             // (the six geometric sums arrive multiplied by the opacity: phase 1 hands over alpha * dL/dalpha)
             const float sx = -acc[0], sy = -acc[1];
@@ -381,58 +327,6 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(8))) void k
             dst[2] = make_float2(-acc[4], -0.5f * acc[5]);
             dst[3] = make_float2(acc[6], __int_as_float(stamp));
         }
-    }
-}
-
-// v_splats[pid] = in-order sum of the pair's slots stamped by this call (k_gather_vtile of gs_blend.hip for 7 values):
-// floats 0-1 mean2d, 2 opacity, 3-5 conic, 9 depth; the colour floats and the padding are written as zeros.
-__global__ __launch_bounds__(256) void k_gather_vtile_depth(int64_t n_pairs, const int32_t* __restrict__ cum,
-                                                            const float* __restrict__ vtile, int stamp, unsigned vt_cap,
-                                                            float4* __restrict__ v_splats) {
-    constexpr int ROW = DACC_VALS;   // odd stride: rows of neighbouring slots fall into different banks
-    __shared__ int sCum[257];
-    __shared__ float sVal[256 * ROW];
-    const int tid = threadIdx.x;
-    const int64_t p0 = (int64_t)blockIdx.x * 256;
-    const int np = (int)min((int64_t)256, n_pairs - p0);
-    if (tid == 0) sCum[0] = p0 == 0 ? 0 : cum[p0 - 1];
-    sCum[tid + 1] = cum[p0 + min(tid, np - 1)];
-    __syncthreads();
-    const int s0 = sCum[0], s1 = sCum[np];
-    const int my_start = sCum[tid], my_end = tid < np ? sCum[tid + 1] : sCum[tid];
-    float acc[DACC_VALS];
-#pragma unroll
-    for (int k = 0; k < DACC_VALS; ++k) acc[k] = 0.f;
-    float2 q0, q1, q2, q3;
-    auto fetch = [&](int u) {
-        q0 = q1 = q2 = q3 = make_float2(0.f, 0.f);   // stamp 0 = never written
-        if (u < s1 && (unsigned)u < vt_cap) {
-            const float2* src = reinterpret_cast<const float2*>(vtile + (int64_t)u * DVT_STRIDE);
-            q0 = src[0]; q1 = src[1]; q2 = src[2]; q3 = src[3];
-        }
-    };
-    fetch(s0 + tid);
-    for (int base = s0; base < s1; base += 256) {
-        const bool live = __float_as_int(q3.y) == stamp;
-        float* row = sVal + tid * ROW;
-        row[0] = live ? q0.x : 0.f; row[1] = live ? q0.y : 0.f; row[2] = live ? q1.x : 0.f;
-        row[3] = live ? q1.y : 0.f; row[4] = live ? q2.x : 0.f; row[5] = live ? q2.y : 0.f;
-        row[6] = live ? q3.x : 0.f;
-        __syncthreads();
-        fetch(base + 256 + tid);
-        const int lo = max(my_start, base) - base, hi = min(my_end, base + 256) - base;
-        for (int r = lo; r < hi; ++r) {
-            const float* src = sVal + r * ROW;
-#pragma unroll
-            for (int k = 0; k < DACC_VALS; ++k) acc[k] += src[k];
-        }
-        __syncthreads();
-    }
-    if (tid < np) {
-        const int64_t pid = p0 + tid;
-        v_splats[pid * 3 + 0] = make_float4(acc[0], acc[1], acc[2], acc[3]);
-        v_splats[pid * 3 + 1] = make_float4(acc[4], acc[5], 0.f, 0.f);
-        v_splats[pid * 3 + 2] = make_float4(0.f, acc[6], 0.f, 0.f);
     }
 }
 
@@ -446,26 +340,21 @@ int st3r_blend_depth_bwd_impl(st3r_ctx* ctx, hipStream_t s, const RasterOut& ro,
         HIP_TRY(hipMemsetAsync(v_splats, 0, sizeof(float) * ST3R_SPLAT_STRIDE * (size_t)n_pairs, s));
         return ST3R_OK;
     }
-    const uint64_t* cmask; int64_t words; const int32_t* tile_nb;
-    int rc = forward_hand_off(ctx, C, tile_w, tile_h, n_isects, &cmask, &words, &tile_nb);
+    // the contribution masks and batch counts st3r_gs_blend_fwd left in the ctx
+    uint64_t* cmask; int64_t words; int32_t* tile_nb;
+    int rc = hand_off_buffers(ctx, C * tile_w * tile_h, n_isects, false, &cmask, &words, &tile_nb);
     if (rc) return rc;
-    // stamped slots of this kernel's own (another stride than the colour backward's): a slot counts only if its stamp is
-    // this call's, so the buffer is cleared only when it is (re)allocated or the counter is about to wrap
-    void* p; int grown = 0;
-    rc = st3r_arena_get2(ctx, SLOT_VTILE_DEPTH, sizeof(float) * DVT_STRIDE * (size_t)n_isects, &p, &grown);
+    // stamped slots of this kernel's own (another stride than the colour backward's, another stamp counter)
+    StampedSlots sl;
+    rc = stamped_slots(ctx, s, SLOT_VTILE_DEPTH, DVT_STRIDE, n_isects, &ctx->depth_stamp, &sl);
     if (rc) return rc;
-    if (grown || ctx->depth_stamp >= 2147483000) {
-        HIP_TRY(hipMemsetAsync(p, 0, ctx->slot_bytes[SLOT_VTILE_DEPTH], s));
-        ctx->depth_stamp = 0;
-    }
-    const int stamp = ++ctx->depth_stamp;
-    const unsigned vt_cap = (unsigned)(ctx->slot_bytes[SLOT_VTILE_DEPTH] / (sizeof(float) * DVT_STRIDE));
     hipLaunchKernelGGL(k_blend_depth_bwd, dim3(C * tile_w * tile_h), dim3(BLK), 0, s, C, ro.W, ro.H, tile_w, tile_h,
                        (const float4*)ro.splats, ro.offsets, ro.flat, end_in_offsets ? -1 : (int)n_isects, alpha, last_ids,
-                       v_depth, cmask, words, tile_nb, cum, ro.rectbase, ro.tight, (float*)p, stamp, vt_cap);
+                       v_depth, cmask, words, tile_nb, cum, ro.rectbase, ro.tight, sl.vtile, sl.stamp, sl.cap);
     LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_gather_vtile_depth, dim3(ceil_div(n_pairs, 256)), dim3(256), 0, s, n_pairs, cum,
-                       (const float*)p, stamp, vt_cap, (float4*)v_splats);
+    // floats 0-1 mean2d, 2 opacity, 3-5 conic, 9 depth; the colour floats and the padding are written as zeros
+    hipLaunchKernelGGL(k_gather_vtile<DACC_VALS>, dim3(ceil_div(n_pairs, 256)), dim3(256), 0, s, n_pairs, cum, sl.vtile,
+                       sl.stamp, sl.cap, (float4*)v_splats);
     LAUNCH_CHECK();
     return ST3R_OK;
 }
@@ -475,10 +364,9 @@ ST3R_EXPORT int st3r_gs_blend_depth_bwd(st3r_ctx* ctx, void* stream, int C, int 
                                         const int32_t* flatten_ids, int64_t n_isects, const float* alpha,
                                         const int32_t* last_ids, const float* v_depth, const int32_t* cum_tiles,
                                         int64_t n_pairs, float* v_splats) {
-    ARG_CHECK(ctx && C > 0 && width > 0 && height > 0 && tile_size == 16);
-    ARG_CHECK(tile_w == (width + 15) / 16 && tile_h == (height + 15) / 16);
-    ARG_CHECK(splats && offsets && alpha && last_ids && v_depth && v_splats && cum_tiles && n_pairs >= 0);
-    ARG_CHECK(n_isects >= 0 && n_isects < 2147483647LL && (n_isects == 0 || flatten_ids));
+    if (int rc = check_blend_args(ctx, C, width, height, tile_size, tile_w, tile_h, splats, offsets, flatten_ids, n_isects))
+        return rc;
+    ARG_CHECK(alpha && last_ids && v_depth && v_splats && cum_tiles && n_pairs >= 0);
     return st3r_blend_depth_bwd_impl(ctx, (hipStream_t)stream,
                                      stage_lists(C, width, height, tile_w, tile_h, splats, offsets, flatten_ids, n_isects,
                                                  cum_tiles, n_pairs),

@@ -14,7 +14,8 @@ with 5e-5 of the tensor's maximum as the floor; the element-wise relative error 
 
 Template instances reached (st3r_blend_bwd_impl):
   * the stand-alone calls: k_blend_fwd<false>, k_blend_bwd<true> (v_alpha given) and k_blend_bwd<false> (None), slot index
-    from reference rectangles;
+    from reference rectangles; the per-pair sums through k_gather_vtile<9>, those of k_blend_depth_bwd through
+    k_gather_vtile<7> (one template, blend_common.h);
   * st3r_gs_raster_train: k_blend_fwd_cells (flag 128: k_blend_fwd<true>) and k_blend_bwd<false> with the packed 10-bit
     `rectbase` (flag 64: `rectbase` NULL, 64-bit packed rectangles).  It never reads debug flag 2 and passes defer == NULL,
     so neither the recomputed tight rectangles nor k_blend_bwd<false, true> (TOUCH) can be reached through it;
