@@ -114,7 +114,9 @@ int st3r_gs_project_sh(st3r_ctx* ctx, void* stream, int N, int C, const float* m
                        float* splats, int32_t* tiles_per_gauss, double* reg_sums);
 
 /* inclusive scan of tiles_per_gauss -> cum_tiles; total copied to *n_isects_host
- * (this call synchronises the stream). gsplat isect_tiles pass 1 + torch.cumsum. */
+ * (this call synchronises the stream). gsplat isect_tiles pass 1 + torch.cumsum.  Counts below 2^20 each.  A total
+ * up to 2^31 - 1 comes back as it is; past that (cum_tiles is int32 and has wrapped) the call returns
+ * ST3R_ERR_INVALID and leaves -1 in *n_isects_host. */
 int st3r_gs_isect_scan(st3r_ctx* ctx, void* stream, int64_t n_pairs, const int32_t* tiles_per_gauss,
                        int32_t* cum_tiles, int64_t* n_isects_host);
 
@@ -305,6 +307,25 @@ int st3r_gs_render(st3r_ctx* ctx, void* stream, int N, int C, const float* means
                    const float* scales, const float* opacities, const float* sh, int sh_stride,
                    const float* viewmats, const float* Ks, const float* campos, int width, int height,
                    float* rgb, float* alpha, int64_t* stats_host);
+
+/* What the front end of a fused call (project -> scan -> emit -> sort -> offsets) of this shape decides on the host,
+ * computed by the code that decides it when the call runs.  Host arithmetic only (no context, no GPU): it is here so that
+ * tests can assert which paths of the kernels their shapes reach.  training: st3r_gs_train_fwd_bwd / st3r_gs_train_step;
+ * records: st3r_gs_raster_train; neither: st3r_gs_render.  n_records: the (record, tile) count of the call -- for a
+ * call that keeps the count on the device, the capacity it sized its buffers for: that is what the tile sort's shape is
+ * decided on (0: entries 14..17 stay 0).  out[0 .. ST3R_FRONT_PLAN_WORDS):
+ *    0 32-bit packed rectangles   1 `rectbase` (slot base | 10-bit rectangle) present   2 32-bit level-1 keys
+ *    3 level-1 sort by camera segments (pass count decided on the device)
+ *    4 tiles of the pair scan     5 emission workgroups per camera   6 emission workgroups   7 they sum their own base
+ *      (0: k_isect_wg_scan runs)
+ *    8 level-1 sort: small tile shape   9 its items per tile   10 its tiles   11 tiles per segment (0: no segments)
+ *      12 its passes (0 with segments)
+ *   13 bits of the (camera, tile) key sorted   14 tile sort: small shape   15 items per tile   16 tiles   17 passes
+ *   20 SCAN_TILE  21 EP  22 ECH  23 EMIT_SELF_BASE_MAX  24 keys per thread of the offsets kernel  25 RS_SMALL_BELOW
+ *   26 / 27 items per small / large sort tile, 32-bit keys   28 / 29 the same, 64-bit keys */
+#define ST3R_FRONT_PLAN_WORDS 32
+int st3r_front_plan(int N, int C, int width, int height, int debug_flags, int training, int records, int64_t n_records,
+                    int64_t* out, int n_out);
 
 /* ------------------------------------------------------------------------------------
  * Path B -- global alignment.  Runs the whole two-stage optimisation of

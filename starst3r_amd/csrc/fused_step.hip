@@ -36,6 +36,46 @@ int st3r_count_settle(st3r_ctx* ctx) {
     return ST3R_OK;
 }
 
+// What rasterize_front decides on the host from the shape of a call alone (the sorts', the scan's and the emission's own
+// shapes come from the functions that launch them).  with_reg: the projection's reduction is at hand (training calls);
+// records: the splat records come from the caller (st3r_gs_raster_train).
+struct FrontPlan {
+    int tile_w, tile_h;
+    bool key32;       // level-1 keys: one 32-bit word (camera | depth code above the near plane's) -- else 64-bit
+    bool segments;    // level-1 sort per camera segment on biased keys, pass count from the device
+    int rect32;       // 32-bit packed rectangles -- else 64-bit
+    bool rectbase;    // slot base | 10-bit rectangle per pair for the blend backward
+    uint32_t key_base;
+    int l1_end_bit;   // bits of the level-1 key sorted when the sort is not segmented: depth code (29 / 32) + camera bits
+    int end_bit;      // bits of the (camera, tile) key
+};
+static const float k_near_plane = 0.01f, k_far_plane = 1e10f;
+static FrontPlan front_plan(int C, int W, int H, int debug_flags, bool with_reg, bool records) {
+    FrontPlan p;
+    const int tile = 16;
+    p.tile_w = (W + tile - 1) / tile; p.tile_h = (H + tile - 1) / tile;
+    // Level-1 keys.  Up to 8 local views: one 32-bit word, camera (3 bits) | depth bits minus those of the near plane
+    // (the reference's near = 0.01 and far = 1e10 span < 2^29 float codes) -- the same order as (camera | depth) at
+    // 8 instead of 12 bytes per pair and one radix pass less.  More views: 64-bit (camera << 32 | depth bits).
+    uint32_t near_bits, far_bits;
+    memcpy(&near_bits, &k_near_plane, 4); memcpy(&far_bits, &k_far_plane, 4);
+    p.key32 = (C <= 8) && (far_bits - near_bits < 0x1FFFFFFFu);
+    p.key_base = p.key32 ? near_bits : 0u;
+    // packed tile rectangle of every pair (pair-id order; the tile count of a pair is the area of its rectangle, no
+    // array of its own): 32-bit entries for tile grids up to 255 x 255 (tile_rect.h), 64-bit beyond -- and under debug
+    // flag 64, whose backward reads the 64-bit form
+    p.rect32 = (p.tile_w <= 255 && p.tile_h <= 255 && !(debug_flags & 64)) ? 1 : 0;
+    // Round 6: with the projection's own reduction at hand (training calls) the level-1 sort runs per camera SEGMENT on keys
+    // biased by the smallest depth code of the call -- three 8-bit passes instead of four whenever the scene's depth codes
+    // span less than 2^24 (decided on the device: counts[8..10] = bias, sentinel, passes); debug flag 4 keeps the
+    // (camera | depth) keys and their four passes
+    p.segments = p.key32 && with_reg && !records && !(debug_flags & 4);
+    p.l1_end_bit = (p.key32 ? 29 : 32) + bit_length_u32((uint32_t)(C - 1));
+    p.rectbase = p.tile_w <= 1023 && p.tile_h <= 1023 && !(debug_flags & 64);   // 10-bit rectangle fields
+    p.end_bit = bit_length_u32((uint32_t)((int64_t)C * p.tile_w * p.tile_h - 1));
+    return p;
+}
+
 // project -> scan -> emit -> sort -> offsets, all in ctx scratch
 static int rasterize_front(st3r_ctx* ctx, hipStream_t s, const GsParams& g, const GsViews& v, double* reg_sums, int tight,
                            const float* records_in, bool allow_async, RasterOut* o, double* loss_sums = nullptr) {
@@ -45,7 +85,8 @@ static int rasterize_front(st3r_ctx* ctx, hipStream_t s, const GsParams& g, cons
     // replaced by k_records_prepare and the records are used in place (g's and v's pointers are not looked at)
     const int N = g.N, C = v.C, W = v.W, H = v.H;
     const int tile = 16;
-    const int tile_w = (W + tile - 1) / tile, tile_h = (H + tile - 1) / tile;
+    const FrontPlan fp = front_plan(C, W, H, ctx->debug_flags, reg_sums != nullptr, records_in != nullptr);
+    const int tile_w = fp.tile_w, tile_h = fp.tile_h;
     const int64_t n_pairs = (int64_t)N * C;
     float* splats = const_cast<float*>(records_in);
     if (!records_in) {
@@ -56,32 +97,21 @@ static int rasterize_front(st3r_ctx* ctx, hipStream_t s, const GsParams& g, cons
     ARENA_GET(SLOT_OFFSETS, int32_t, (int64_t)C * tile_w * tile_h + 1, offsets);   // + the total (closes the last tile)
     // Two-level sort (see gs_isect.hip): pairs by (camera | depth) first, then the emitted records by
     // their 32-bit (camera, tile) key with a stable sort -- the same final order as gsplat's single
-    // 64-bit (camera | tile | depth) sort at roughly a quarter of the sort traffic.
-    // Level-1 keys.  Up to 8 local views: one 32-bit word, camera (3 bits) | depth bits minus those of the near plane
-    // (the reference's near = 0.01 and far = 1e10 span < 2^29 float codes) -- the same order as (camera | depth) at
-    // 8 instead of 12 bytes per pair and one radix pass less.  More views: 64-bit (camera << 32 | depth bits).
-    const float near_plane = 0.01f, far_plane = 1e10f;
-    uint32_t near_bits, far_bits;
-    memcpy(&near_bits, &near_plane, 4); memcpy(&far_bits, &far_plane, 4);
-    const bool key32 = (C <= 8) && (far_bits - near_bits < 0x1FFFFFFFu);
+    // 64-bit (camera | tile | depth) sort at roughly a quarter of the sort traffic.  (The forms of the level-1 keys, of the
+    // packed rectangles and of the level-1 sort: front_plan.)
+    const float near_plane = k_near_plane, far_plane = k_far_plane;
+    const bool key32 = fp.key32;
     ARENA_GET(SLOT_DKEYS_A, uint64_t, n_pairs, dkeys_a);
     ARENA_GET(SLOT_DKEYS_B, uint64_t, n_pairs, dkeys_b);
     ARENA_GET(SLOT_DVALS_A, int32_t, n_pairs, dvals_a);
     ARENA_GET(SLOT_DVALS_B, int32_t, n_pairs, perm);
-    // packed tile rectangle of every pair (pair-id order; the tile count of a pair is the area of its rectangle, no
-    // array of its own): 32-bit entries for tile grids up to 255 x 255 (tile_rect.h), 64-bit beyond -- and under debug
-    // flag 64, whose backward reads the 64-bit form
-    const int rect32 = (tile_w <= 255 && tile_h <= 255 && !(ctx->debug_flags & 64)) ? 1 : 0;
+    const int rect32 = fp.rect32;
     ARENA_GET(SLOT_RECTS, uint64_t, rect32 ? (n_pairs + 1) / 2 : n_pairs, rects);
     int32_t* counts = nullptr;
     { int rc_ = st3r_counts_buffer(ctx, s, &counts); if (rc_) return rc_; }
-    // Round 6: with the projection's own reduction at hand (training calls) the level-1 sort runs per camera SEGMENT on keys
-    // biased by the smallest depth code of the call -- three 8-bit passes instead of four whenever the scene's depth codes
-    // span less than 2^24 (decided on the device: counts[8..10] = bias, sentinel, passes); debug flag 4 keeps the
-    // (camera | depth) keys and their four passes
-    uint32_t* const krange = (key32 && reg_sums && !records_in && !(ctx->debug_flags & 4)) ? (uint32_t*)(counts + 8) : nullptr;
+    uint32_t* const krange = fp.segments ? (uint32_t*)(counts + 8) : nullptr;   // counts[8..10] = bias, sentinel, passes
     st3r_prof_begin(ctx, s, STG_PROJECT);
-    const uint32_t key_base = key32 ? near_bits : 0u;
+    const uint32_t key_base = fp.key_base;
     int rc = records_in
                  ? st3r_records_prepare_impl(s, N, C, splats, tile, tile_w, tile_h, tight, nullptr, dkeys_a, dvals_a,
                                              key_base, rects, rect32)
@@ -91,12 +121,11 @@ static int rasterize_front(st3r_ctx* ctx, hipStream_t s, const GsParams& g, cons
     st3r_prof_end(ctx, s, STG_PROJECT);
     if (rc) return rc;
     st3r_prof_begin(ctx, s, STG_SORT_DEPTH);
-    const int cam_bits = bit_length_u32((uint32_t)(C - 1));
     // (segments: the keys WITHOUT the camera bits, one segment of N pairs per camera, biased and sorted in as many 8-bit
     // passes as the depth range of the call needs -- radix_sort.hip: SEG)
     rc = krange ? st3r_radix_sort_u32_segments(ctx, s, N, C, (uint32_t*)dkeys_a, dvals_a, (uint32_t*)dkeys_b, perm, krange)
-         : key32 ? st3r_radix_sort_u32(ctx, s, n_pairs, 0, 29 + cam_bits, (uint32_t*)dkeys_a, dvals_a, (uint32_t*)dkeys_b, perm)
-                 : st3r_radix_sort_u64(ctx, s, n_pairs, 0, 32 + cam_bits, dkeys_a, dvals_a, dkeys_b, perm);
+         : key32 ? st3r_radix_sort_u32(ctx, s, n_pairs, 0, fp.l1_end_bit, (uint32_t*)dkeys_a, dvals_a, (uint32_t*)dkeys_b, perm)
+                 : st3r_radix_sort_u64(ctx, s, n_pairs, 0, fp.l1_end_bit, dkeys_a, dvals_a, dkeys_b, perm);
     st3r_prof_end(ctx, s, STG_SORT_DEPTH);
     if (rc) return rc;
     int64_t n_isects = 0;
@@ -104,7 +133,7 @@ static int rasterize_front(st3r_ctx* ctx, hipStream_t s, const GsParams& g, cons
     // pair-id order scan: slot base of every pair for the backward pass's per-(record, tile) partials
     // (the same launch leaves slot base | rectangle as one word per pair for the backward's staging)
     uint64_t* rectbase = nullptr;
-    if (tile_w <= 1023 && tile_h <= 1023 && !(ctx->debug_flags & 64)) {   // 10-bit rectangle fields
+    if (fp.rectbase) {
         ARENA_GET(SLOT_RECTBASE, uint64_t, n_pairs, rb);
         rectbase = rb;
     }
@@ -154,7 +183,7 @@ static int rasterize_front(st3r_ctx* ctx, hipStream_t s, const GsParams& g, cons
         rc = st3r_isect_emit_chain_impl(ctx, s, N, C, perm, rects, rect32, tile_w, tile_h, tkeys_a, vals_a, n_isects);
         st3r_prof_end(ctx, s, STG_EMIT);
         if (rc) return rc;
-        const int end_bit = bit_length_u32((uint32_t)((int64_t)C * tile_w * tile_h - 1));
+        const int end_bit = fp.end_bit;
         st3r_prof_begin(ctx, s, STG_SORT);
         rc = st3r_sort_tile_impl(ctx, s, n_isects, end_bit, tkeys_a, vals_a, tkeys_b, vals_b, total_dev);
         st3r_prof_end(ctx, s, STG_SORT);
@@ -511,5 +540,41 @@ ST3R_EXPORT int st3r_gs_render(st3r_ctx* ctx, void* stream, int N, int C, const 
     if (stats_host) {
         stats_host[0] = -1; stats_host[1] = ro.n_records; stats_host[2] = st3r_ctx_arena_bytes(ctx); stats_host[3] = 0;
     }
+    return ST3R_OK;
+}
+
+// The host-side decisions of the front end for a call of this shape, read back for the tests (no context, no GPU): every
+// entry comes from the function that takes the decision when the call runs -- front_plan, st3r_scan_tiles, st3r_emit_grid,
+// st3r_radix_sort_shape, st3r_sort_tile_end_bit -- so a retuned constant or a moved threshold changes what this reports.
+ST3R_EXPORT int st3r_front_plan(int N, int C, int width, int height, int debug_flags, int training, int records,
+                                int64_t n_records, int64_t* out, int n_out) {
+    ARG_CHECK(N > 0 && C > 0 && C <= ST3R_MAX_VIEWS && width > 0 && height > 0 && n_records >= 0 && out &&
+              n_out >= ST3R_FRONT_PLAN_WORDS && !(training && records));
+    const FrontPlan fp = front_plan(C, width, height, debug_flags, training != 0, records != 0);
+    const int64_t n_pairs = (int64_t)N * C;
+    for (int i = 0; i < n_out; ++i) out[i] = 0;
+    out[0] = fp.rect32; out[1] = fp.rectbase; out[2] = fp.key32; out[3] = fp.segments;
+    out[4] = st3r_scan_tiles(n_pairs);
+    int bpc, grid, self_base;
+    st3r_emit_grid(N, C, &bpc, &grid, &self_base);
+    out[5] = bpc; out[6] = grid; out[7] = self_base;
+    int64_t sh[8];
+    // the level-1 sort: segments, or the (camera | depth) keys on fp.l1_end_bit bits
+    if (fp.segments) st3r_radix_sort_shape(4, n_pairs, N, C, 0, 0, sh);
+    else st3r_radix_sort_shape(fp.key32 ? 4 : 8, n_pairs, 0, 0, 0, fp.l1_end_bit, sh);
+    out[8] = sh[0]; out[9] = sh[1]; out[10] = sh[2]; out[11] = sh[3]; out[12] = sh[4];
+    out[25] = sh[5];
+    out[fp.key32 ? 26 : 28] = sh[6]; out[fp.key32 ? 27 : 29] = sh[7];
+    st3r_radix_sort_shape(fp.key32 ? 8 : 4, 1, 0, 0, 0, 8, sh);   // (the other key width's two tile sizes)
+    out[fp.key32 ? 28 : 26] = sh[6]; out[fp.key32 ? 29 : 27] = sh[7];
+    // the tile sort over n_records (camera, tile) keys (a call with the count on the device decides on its capacity)
+    out[13] = st3r_sort_tile_end_bit(fp.end_bit);
+    if (n_records > 0) {
+        st3r_radix_sort_shape(4, n_records, 0, 0, 0, (int)out[13], sh);
+        out[14] = sh[0]; out[15] = sh[1]; out[16] = sh[2]; out[17] = sh[4];
+    }
+    int64_t k[5];
+    st3r_isect_constants(k);
+    for (int i = 0; i < 5; ++i) out[20 + i] = k[i];
     return ST3R_OK;
 }

@@ -209,12 +209,14 @@ static int chain_ctl(st3r_ctx* ctx, hipStream_t s, int64_t nwords, ChainCtl* c) 
     return ST3R_OK;
 }
 
+int st3r_scan_tiles(int64_t n) { return ceil_div(n, SCAN_TILE); }
+
 // out = inclusive scan of in (counts) or of the areas of the packed rectangles `rects`; the grand total is left in
 // device memory (*total_dev)
 static int st3r_scan_inclusive_i32(st3r_ctx* ctx, hipStream_t s, const int32_t* in, const void* rects, int rect32,
                                    int32_t* out, int64_t n, int32_t** total_dev, uint64_t* pack_out = nullptr,
                                    int32_t* total_copy = nullptr, int32_t* total_host = nullptr) {
-    const int ntiles = ceil_div(n, SCAN_TILE);
+    const int ntiles = st3r_scan_tiles(n);
     ChainCtl c;
     int rc = chain_ctl(ctx, s, ntiles, &c);
     if (rc) return rc;
@@ -253,8 +255,13 @@ int st3r_isect_scan_impl(st3r_ctx* ctx, hipStream_t s, int64_t n_pairs, const in
 ST3R_EXPORT int st3r_gs_isect_scan(st3r_ctx* ctx, void* stream, int64_t n_pairs, const int32_t* tiles_per_gauss,
                                    int32_t* cum_tiles, int64_t* n_isects_host) {
     ARG_CHECK(ctx && n_pairs >= 0 && tiles_per_gauss && cum_tiles && n_isects_host);
-    return st3r_isect_scan_impl(ctx, (hipStream_t)stream, n_pairs, tiles_per_gauss, cum_tiles, n_isects_host, nullptr,
-                                0, nullptr, nullptr, nullptr, nullptr);
+    int rc = st3r_isect_scan_impl(ctx, (hipStream_t)stream, n_pairs, tiles_per_gauss, cum_tiles, n_isects_host, nullptr,
+                                  0, nullptr, nullptr, nullptr, nullptr);
+    if (!rc && *n_isects_host < 0) {   // (the kernel reports a total past 2^31 - 1 as -1: cum_tiles has wrapped)
+        st3r_set_error("more than 2^31 - 1 tile intersections in one call: split the views over more calls / GPUs");
+        rc = ST3R_ERR_INVALID;
+    }
+    return rc;
 }
 
 __global__ __launch_bounds__(256) void k_isect_emit(int N, int64_t n_pairs, const float4* __restrict__ splats,
@@ -358,12 +365,13 @@ ST3R_EXPORT int st3r_gs_offsets(st3r_ctx* ctx, void* stream, int64_t n_isects, c
 // on pair id, steps 2/3 preserve it.
 // ------------------------------------------------------------------------------------
 // offsets[k] = first sorted position whose 32-bit (camera, tile) key is >= k
+#define OFFSET_KEYS 4
 __global__ __launch_bounds__(256) void k_isect_offsets32(int64_t n_isects, const uint32_t* __restrict__ keys,
                                                          int64_t total, int32_t* __restrict__ offsets,
                                                          const int32_t* __restrict__ n_dev) {
     // n_dev: the record count lives on the device (n_isects is then the launch capacity); offsets has total + 1
     // entries, the last one = the record count (end of the last tile for the blend kernels).  Four keys per thread
-    // (one 16-byte load) plus the key in front of them.
+    // (one 16-byte load; OFFSET_KEYS, which sizes the grid) plus the key in front of them.
     if (n_dev) n_isects = min(n_isects, (int64_t)max(*n_dev, 0));
     const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (n_isects == 0) {
@@ -402,7 +410,7 @@ int st3r_isect_offsets32_impl(hipStream_t s, int64_t n_isects, const uint32_t* k
         HIP_TRY(hipMemsetAsync(offsets, 0, sizeof(int32_t) * (size_t)(total + 1), s));
         return ST3R_OK;
     }
-    hipLaunchKernelGGL(k_isect_offsets32, dim3(ceil_div(n_isects > 0 ? (n_isects + 3) / 4 : 1, 256)), dim3(256), 0, s, n_isects,
+    hipLaunchKernelGGL(k_isect_offsets32, dim3(ceil_div(n_isects > 0 ? (n_isects + OFFSET_KEYS - 1) / OFFSET_KEYS : 1, 256)), dim3(256), 0, s, n_isects,
                        keys, total, offsets, n_dev);
     LAUNCH_CHECK();
     return ST3R_OK;
@@ -689,12 +697,23 @@ __global__ __launch_bounds__(256) void k_isect_emit_d(int N, int C, int bpc, con
     }
 }
 
+// the emission grid: workgroups per camera, workgroups in all, and whether every workgroup sums its own base (no scan launch)
+void st3r_emit_grid(int N, int C, int* bpc, int* grid, int* self_base) {
+    *bpc = ceil_div(N, EP);
+    *grid = C * *bpc;
+    *self_base = *grid <= EMIT_SELF_BASE_MAX ? 1 : 0;
+}
+
+void st3r_isect_constants(int64_t out[5]) {
+    out[0] = SCAN_TILE; out[1] = EP; out[2] = ECH; out[3] = EMIT_SELF_BASE_MAX; out[4] = OFFSET_KEYS;
+}
+
 int st3r_isect_emit_chain_impl(st3r_ctx* ctx, hipStream_t s, int N, int C, const int32_t* perm, const void* rects,
                                int rect32, int tile_w, int tile_h, uint32_t* tile_keys, int32_t* vals, int64_t cap) {
     const int64_t n_pairs = (int64_t)N * C;
     if (n_pairs == 0) return ST3R_OK;
-    const int bpc = ceil_div(N, EP);
-    const int grid = C * bpc;
+    int bpc, grid, self_base_i;
+    st3r_emit_grid(N, C, &bpc, &grid, &self_base_i);
     void* p;
     int rc = st3r_arena_get(ctx, SLOT_RECTS_D, (rect32 ? sizeof(uint32_t) : sizeof(uint64_t)) * (size_t)n_pairs, &p);
     if (rc) return rc;
@@ -705,7 +724,7 @@ int st3r_isect_emit_chain_impl(st3r_ctx* ctx, hipStream_t s, int N, int C, const
     int32_t* wg_tiles = (int32_t*)(wg_base + grid);   // (8-byte entries in front: 16-byte aligned for even grids -- see below)
     if (((uintptr_t)wg_tiles & 15) != 0) wg_tiles += 2;
     hipLaunchKernelGGL(k_isect_gather, dim3(grid), dim3(256), 0, s, N, C, bpc, perm, rects, rect32, rects_d, wg_tiles);
-    const bool self_base = grid <= EMIT_SELF_BASE_MAX;
+    const bool self_base = self_base_i != 0;
     if (!self_base) hipLaunchKernelGGL(k_isect_wg_scan, dim3(1), dim3(1024), 0, s, grid, wg_tiles, wg_base);
     hipLaunchKernelGGL(k_isect_emit_d, dim3(grid), dim3(256), 0, s, N, C, bpc, perm, rects_d, rect32,
                        self_base ? (const long long*)nullptr : wg_base, wg_tiles, tile_w, tile_h, tile_keys, vals, cap);

@@ -14,12 +14,14 @@ static int st3r_sort_impl(st3r_ctx* ctx, hipStream_t s, int64_t n, int end_bit, 
                                reinterpret_cast<uint64_t*>(keys_out), vals_out);
 }
 
+// one view of one tile: the only key is 0 and the callers' end_bit = bit_length(C * tiles - 1) is 0, which the radix
+// sort rejects as an empty bit range; one stable pass over bit 0 carries the pairs across in their depth order
+int st3r_sort_tile_end_bit(int end_bit) { return end_bit < 1 ? 1 : end_bit; }
+
 // 32-bit (camera, tile) keys, stable: keeps the depth order established by the first level
 int st3r_sort_tile_impl(st3r_ctx* ctx, hipStream_t s, int64_t n, int end_bit, uint32_t* keys_in, int32_t* vals_in,
                         uint32_t* keys_out, int32_t* vals_out, const int32_t* n_dev) {
-    // one view of one tile: the only key is 0 and the callers' end_bit = bit_length(C * tiles - 1) is 0, which the radix
-    // sort rejects as an empty bit range; one stable pass over bit 0 carries the pairs across in their depth order
-    if (end_bit < 1) end_bit = 1;
+    end_bit = st3r_sort_tile_end_bit(end_bit);
     if (n_dev) return st3r_radix_sort_u32_devcount(ctx, s, n, n_dev, 0, end_bit, keys_in, vals_in, keys_out, vals_out);
     return st3r_radix_sort_u32(ctx, s, n, 0, end_bit, keys_in, vals_in, keys_out, vals_out);
 }

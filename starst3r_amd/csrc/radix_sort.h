@@ -19,3 +19,7 @@ int st3r_radix_sort_u32_devcount(st3r_ctx* ctx, hipStream_t s, int64_t n_cap, co
 // three read from device memory (written by the projection's reduction: gs_project.hip)
 int st3r_radix_sort_u32_segments(st3r_ctx* ctx, hipStream_t s, int64_t seg_n, int n_seg, const uint32_t* keys_in,
                                  const int32_t* vals_in, uint32_t* keys_out, int32_t* vals_out, const uint32_t* krange);
+// The host-side decisions of a sort, for st3r_front_plan (fused_step.hip): out = small shape?, items per tile, tiles,
+// tiles per segment (seg_n > 0: n_seg segments of seg_n items), passes (0 for segments: decided on the device), then the
+// constants RS_SMALL_BELOW and the items per tile of the small and the large shape.  Computed by the code that launches.
+void st3r_radix_sort_shape(int key_bytes, int64_t n, int64_t seg_n, int n_seg, int begin_bit, int end_bit, int64_t out[8]);

@@ -370,17 +370,31 @@ __global__ __launch_bounds__(THREADS) void k_rs_pass(const K* __restrict__ kin, 
 
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
+// The tile shape of a sort of n items (seg_n > 0: n_seg segments of seg_n items each, n = seg_n * n_seg), decided on the
+// host here and nowhere else: sort_pairs and sort_pairs_seg launch what it says, st3r_radix_sort_shape reads it back.
+struct SortShape { bool small; int64_t tile, ntiles; int tiles_per_seg; };
+template <typename K>
+SortShape sort_shape(int64_t n, int64_t seg_n = 0, int n_seg = 0) {
+    constexpr int TILE_L = THREADS_L * Traits<K>::IPT, TILE_S = THREADS_S * Traits<K>::IPT_S;
+    SortShape sh;
+    sh.small = (n + TILE_L - 1) / TILE_L < RS_SMALL_BELOW;   // (with a device count: decided on the capacity)
+    sh.tile = sh.small ? TILE_S : TILE_L;
+    sh.tiles_per_seg = seg_n > 0 ? (int)((seg_n + sh.tile - 1) / sh.tile) : 0;
+    sh.ntiles = seg_n > 0 ? (int64_t)sh.tiles_per_seg * n_seg : (n + sh.tile - 1) / sh.tile;
+    return sh;
+}
+inline int sort_passes(int begin_bit, int end_bit) { return (end_bit - begin_bit + RB - 1) / RB; }
+
 template <typename K>
 int sort_pairs(st3r_ctx* ctx, hipStream_t s, int64_t n, int begin_bit, int end_bit, const K* keys_in,
                const int32_t* vals_in, K* keys_out, int32_t* vals_out, const int32_t* n_dev = nullptr) {
     if (n == 0) return ST3R_OK;
     if (end_bit > (int)sizeof(K) * 8) end_bit = (int)sizeof(K) * 8;
     if (begin_bit < 0 || begin_bit >= end_bit) { st3r_set_error("radix sort: empty bit range"); return ST3R_ERR_INVALID; }
-    const int passes = (end_bit - begin_bit + RB - 1) / RB;
-    constexpr int TILE_L = THREADS_L * Traits<K>::IPT, TILE_S = THREADS_S * Traits<K>::IPT_S;
-    const bool small = (n + TILE_L - 1) / TILE_L < RS_SMALL_BELOW;   // (with a device count: decided on the capacity)
-    const int64_t TILE = small ? TILE_S : TILE_L;
-    const int64_t ntiles = (n + TILE - 1) / TILE;
+    const int passes = sort_passes(begin_bit, end_bit);
+    const SortShape sh = sort_shape<K>(n);
+    const bool small = sh.small;
+    const int64_t ntiles = sh.ntiles;
     const size_t hist_bytes = align256(sizeof(uint32_t) * (size_t)(HIST_COPIES * MAX_PASSES * RADIX + MAX_PASSES));
     const size_t status_bytes = sizeof(u64) * (size_t)passes * (size_t)ntiles * RADIX;
     const size_t meta_bytes = hist_bytes + align256(status_bytes);
@@ -428,12 +442,11 @@ int sort_pairs_seg(st3r_ctx* ctx, hipStream_t s, int64_t seg_n, int n_seg, const
     if (seg_n == 0 || n_seg == 0) return ST3R_OK;
     typedef uint32_t K;
     constexpr int PASSES = 4;   // launches; the passes that run: krange[2]
-    constexpr int TILE_L = THREADS_L * Traits<K>::IPT, TILE_S = THREADS_S * Traits<K>::IPT_S;
     const int64_t n = seg_n * n_seg;
-    const bool small = (n + TILE_L - 1) / TILE_L < RS_SMALL_BELOW;
-    const int64_t TILE = small ? TILE_S : TILE_L;
-    const int tiles_per_seg = (int)((seg_n + TILE - 1) / TILE);
-    const int64_t ntiles = (int64_t)tiles_per_seg * n_seg;
+    const SortShape sh = sort_shape<K>(n, seg_n, n_seg);
+    const bool small = sh.small;
+    const int tiles_per_seg = sh.tiles_per_seg;
+    const int64_t ntiles = sh.ntiles;
     const size_t hist_bytes = align256(sizeof(uint32_t) * ((size_t)n_seg * MAX_PASSES * RADIX + MAX_PASSES));
     const size_t status_bytes = sizeof(u64) * (size_t)PASSES * (size_t)ntiles * RADIX;
     const size_t meta_bytes = hist_bytes + align256(status_bytes);
@@ -464,6 +477,16 @@ int sort_pairs_seg(st3r_ctx* ctx, hipStream_t s, int64_t seg_n, int n_seg, const
 }
 
 }  // namespace
+
+void st3r_radix_sort_shape(int key_bytes, int64_t n, int64_t seg_n, int n_seg, int begin_bit, int end_bit, int64_t out[8]) {
+    if (end_bit > 8 * key_bytes) end_bit = 8 * key_bytes;
+    const SortShape sh = key_bytes == 4 ? sort_shape<uint32_t>(n, seg_n, n_seg) : sort_shape<uint64_t>(n, seg_n, n_seg);
+    out[0] = sh.small ? 1 : 0; out[1] = sh.tile; out[2] = sh.ntiles; out[3] = sh.tiles_per_seg;
+    out[4] = seg_n > 0 ? 0 : sort_passes(begin_bit, end_bit);   // (segments: the pass count is decided on the device)
+    out[5] = RS_SMALL_BELOW;
+    out[6] = key_bytes == 4 ? THREADS_S * Traits<uint32_t>::IPT_S : THREADS_S * Traits<uint64_t>::IPT_S;
+    out[7] = key_bytes == 4 ? THREADS_L * Traits<uint32_t>::IPT : THREADS_L * Traits<uint64_t>::IPT;
+}
 
 int st3r_radix_sort_u32_segments(st3r_ctx* ctx, hipStream_t s, int64_t seg_n, int n_seg, const uint32_t* keys_in,
                                  const int32_t* vals_in, uint32_t* keys_out, int32_t* vals_out, const uint32_t* krange) {

@@ -66,6 +66,11 @@ int st3r_project_sh_bwd_impl(hipStream_t s, const GsParams& g, const GsViews& v,
 int st3r_isect_scan_impl(st3r_ctx* ctx, hipStream_t s, int64_t n_pairs, const int32_t* tiles, int32_t* cum,
                          int64_t* n_isects_host, const void* pack_rects, int rect32, uint64_t* pack_out,
                          int32_t** total_dev_out, int32_t* total_copy, int32_t* total_host);
+// host-side decisions, shared with st3r_front_plan: tiles of the single-pass scan, the emission grid, the tiling constants
+// (SCAN_TILE, EP, ECH, EMIT_SELF_BASE_MAX, keys per thread of k_isect_offsets32)
+int st3r_scan_tiles(int64_t n);
+void st3r_emit_grid(int N, int C, int* bpc, int* grid, int* self_base);
+void st3r_isect_constants(int64_t out[5]);
 int st3r_isect_emit_chain_impl(st3r_ctx* ctx, hipStream_t s, int N, int C, const int32_t* perm, const void* rects,
                                int rect32, int tile_w, int tile_h, uint32_t* tile_keys, int32_t* vals, int64_t cap);
 int st3r_records_prepare_impl(hipStream_t s, int N, int C, const float* splats, int tile_size, int tile_w, int tile_h,
@@ -73,6 +78,7 @@ int st3r_records_prepare_impl(hipStream_t s, int N, int C, const float* splats, 
                               void* rects, int rect32);
 int st3r_isect_offsets32_impl(hipStream_t s, int64_t n_isects, const uint32_t* keys, int C, int tile_w, int tile_h,
                               int32_t* offsets, const int32_t* n_dev);
+int st3r_sort_tile_end_bit(int end_bit);
 int st3r_sort_tile_impl(st3r_ctx* ctx, hipStream_t s, int64_t n, int end_bit, uint32_t* keys_in, int32_t* vals_in,
                         uint32_t* keys_out, int32_t* vals_out, const int32_t* n_dev);
 

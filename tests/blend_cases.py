@@ -155,25 +155,42 @@ def fused_kept_depths(case):
     centres the box around {alpha >= 1/255} reaches (tile_rect.h: tight_tile_rect), evaluated in float64.  The cases keep
     every box edge >= 0.04 px away from a pixel centre, so float32 decides alike."""
     out = np.zeros((case.Cn, case.th, case.tw), int)
-    for k in range(case.Cn * case.N):
-        rad = int(case.radii[k])
-        if rad <= 0:
-            continue
-        x, y = float(case.means2d[k, 0]), float(case.means2d[k, 1]); op = float(case.opacities[k])
-        a, b, c = (float(v) for v in case.conics[k])
-        if not (255.0 * op > 1.0):
-            continue
-        cl = lambda v, hi: 0 if not v > 0 else (hi if v >= hi else int(v))
-        x0 = cl(math.floor((x - rad) / 16), case.tw); x1 = cl(math.ceil((x + rad) / 16), case.tw)
-        y0 = cl(math.floor((y - rad) / 16), case.th); y1 = cl(math.ceil((y + rad) / 16), case.th)
-        det = a * c - b * b
-        tau = math.log(255.0 * op) * (1.0002 + 4e-6 * a * c / det) + 1e-4
-        ex = math.sqrt(2 * tau / det * c) * 1.0001 + 0.05; ey = math.sqrt(2 * tau / det * a) * 1.0001 + 0.05
-        x0 = max(x0, max(math.ceil((x - ex - 15.5) / 16), -1)); x1 = min(x1, math.floor((x + ex - 0.5) / 16) + 1)
-        y0 = max(y0, max(math.ceil((y - ey - 15.5) / 16), -1)); y1 = min(y1, math.floor((y + ey - 0.5) / 16) + 1)
+    ref, tight = tile_rects(case.means2d, case.radii, case.opacities, case.conics, case.tw, case.th)
+    for k in np.nonzero(case.radii > 0)[0]:
+        x0, x1, y0, y1 = (int(v) for v in tight[k])
         if x1 > x0 and y1 > y0:
             out[case.camera_ids[k], y0:y1, x0:x1] += 1
     return out.reshape(-1).tolist()
+
+
+def tile_rects(means2d, radii, opacities, conics, tw, th):
+    """(reference rectangles, tight rectangles), each [n, 4] = x0, x1, y0, y1 in tiles, float64 evaluation of tile_rect.h:
+    ref_tile_rect, and tight_tile_rect applied to it (constants included).  A pair with radius <= 0 has the empty rectangle
+    (0, 0, 0, 0) in both; one whose opacity can never pass 1/255 has an empty tight rectangle.  Shared by fused_kept_depths
+    and by front_cases.py, whose cases must keep tight == reference for every live pair."""
+    x = np.asarray(means2d, np.float64)[:, 0]; y = np.asarray(means2d, np.float64)[:, 1]
+    rad = np.asarray(radii).astype(np.float64); op = np.asarray(opacities, np.float64)
+    a, b, c = (np.asarray(conics, np.float64)[:, i] for i in range(3))
+    live = rad > 0
+
+    def cl(v, hi):   # tile_clampi
+        return np.where(~(v > 0), 0, np.where(v >= hi, hi, np.trunc(v))).astype(np.int64)
+    x0 = cl(np.floor((x - rad) / 16), tw); x1 = cl(np.ceil((x + rad) / 16), tw)
+    y0 = cl(np.floor((y - rad) / 16), th); y1 = cl(np.ceil((y + rad) / 16), th)
+    ref = np.stack([x0, x1, y0, y1], 1) * live[:, None]
+    vis = live & (255.0 * op > 1.0)
+    with np.errstate(all="ignore"):
+        det = a * c - b * b
+        tau = np.log(np.where(vis, 255.0 * op, 2.0)) * (1.0002 + 4e-6 * a * c / det) + 1e-4
+        ex = np.sqrt(2 * tau / det * c) * 1.0001 + 0.05; ey = np.sqrt(2 * tau / det * a) * 1.0001 + 0.05
+        i64 = lambda v: np.where(vis, v, 0).astype(np.int64)
+        tx0 = np.maximum(x0, np.maximum(i64(np.ceil((x - ex - 15.5) / 16)), -1))
+        tx1 = np.minimum(x1, i64(np.minimum(np.floor((x + ex - 0.5) / 16), 1.0e6)) + 1)
+        ty0 = np.maximum(y0, np.maximum(i64(np.ceil((y - ey - 15.5) / 16)), -1))
+        ty1 = np.minimum(y1, i64(np.minimum(np.floor((y + ey - 0.5) / 16), 1.0e6)) + 1)
+    tx1 = np.maximum(tx1, tx0); ty1 = np.maximum(ty1, ty0)
+    tight = np.stack([tx0, tx1, ty0, ty1], 1) * vis[:, None]
+    return ref, tight
 
 
 # ---------------------------------------------------------------------------------------------------------------------
