@@ -31,6 +31,7 @@
 #include "stages.h"
 #include "tile_rect.h"
 #include "blend_common.h"
+#include "project_common.h"
 
 // q-form of record `id` in LDS slot t, two words: (x y opacity qa | qb qc z -) with qa, qb, qc formed exactly as
 // stage_qform forms them; returns the 4-bit quadrant relevance
@@ -411,7 +412,6 @@ __global__ __launch_bounds__(256) void k_depth_bwd(int N, int C, const float* __
                                                    float* __restrict__ grads, double* __restrict__ part) {
     __shared__ double red[4 * DPOSE_VALS];
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     float mx = 0.f, my = 0.f, mz = 0.f;
     if (g < N) { mx = means[3 * g]; my = means[3 * g + 1]; mz = means[3 * g + 2]; }
     float ax = 0.f, ay = 0.f, az = 0.f;
@@ -423,22 +423,9 @@ __global__ __launch_bounds__(256) void k_depth_bwd(int N, int C, const float* __
         ax = fmaf(V[8], vz, ax); ay = fmaf(V[9], vz, ay); az = fmaf(V[10], vz, az);
         if (part) {   // (uniform over the launch)
             double v[DPOSE_VALS] = {(double)vz * (double)mx, (double)vz * (double)my, (double)vz * (double)mz, (double)vz};
-#pragma unroll
-            for (int k = 0; k < DPOSE_VALS; ++k) {
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_xor(v[k], off, 64);
-            }
             __syncthreads();   // the previous camera's partial has been read
-            if (lane == 0) {
-#pragma unroll
-                for (int k = 0; k < DPOSE_VALS; ++k) red[wv * DPOSE_VALS + k] = v[k];
-            }
-            __syncthreads();
-            if (threadIdx.x < DPOSE_VALS) {
-                const int k = threadIdx.x;
-                part[((int64_t)c * gridDim.x + blockIdx.x) * DPOSE_VALS + k] =
-                    ((red[k] + red[DPOSE_VALS + k]) + red[2 * DPOSE_VALS + k]) + red[3 * DPOSE_VALS + k];
-            }
+            const double sum = block_sum_fixed(v, red);
+            if (threadIdx.x < DPOSE_VALS) part[((int64_t)c * gridDim.x + blockIdx.x) * DPOSE_VALS + threadIdx.x] = sum;
         }
     }
     if (g < N) { grads[3 * g] += ax; grads[3 * g + 1] += ay; grads[3 * g + 2] += az; }
@@ -449,26 +436,15 @@ __global__ __launch_bounds__(256) void k_depth_bwd_finish(int n_part, const doub
                                                           float* __restrict__ v_viewmats) {
     __shared__ double red[4 * DPOSE_VALS];
     const int c = blockIdx.x;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     double v[DPOSE_VALS] = {0.0, 0.0, 0.0, 0.0};
     const double* pc = part + (int64_t)c * n_part * DPOSE_VALS;
     for (int b = threadIdx.x; b < n_part; b += blockDim.x) {
 #pragma unroll
         for (int k = 0; k < DPOSE_VALS; ++k) v[k] += pc[(int64_t)b * DPOSE_VALS + k];
     }
-#pragma unroll
-    for (int k = 0; k < DPOSE_VALS; ++k) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_xor(v[k], off, 64);
-    }
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < DPOSE_VALS; ++k) red[wv * DPOSE_VALS + k] = v[k];
-    }
-    __syncthreads();
+    const double sum = block_sum_fixed(v, red);
     if (threadIdx.x < DPOSE_VALS) {
         const int k = threadIdx.x;
-        const double sum = ((red[k] + red[DPOSE_VALS + k]) + red[2 * DPOSE_VALS + k]) + red[3 * DPOSE_VALS + k];
         float* dst = v_viewmats + 16 * c + 8 + k;
         *dst = (float)((double)*dst + sum);
     }

@@ -9,37 +9,24 @@
 // Per camera, through campos = inverse(V)[:3, 3]:
 //     v_V = [[v_R, v_t], [0, 0]] - (V^-T [v_campos; 0]) (x) inverse(V)[:, 3]
 //
-// k_project_sh_bwd is left as it is (its GATHER form is the tuned training kernel): the ~45 lines of chain rule are
-// restated here rather than shared.
+// The conic chain rule (conic_chain) is project_common.h's, shared with k_project_sh_bwd.  The rest of the per-pair
+// arithmetic is still written out in both kernels and must be kept equal by hand: a shared function for it changes the
+// machine code of k_project_sh_bwd, the tuned training kernel ("What the projection kernels share").
 //
 // Reduction without float atomics (bit-reproducible, like every backward here): grid (blocks of 256 Gaussians, C);
 // each block sums its 256 pairs' 15 terms in double in a fixed order (wave butterfly, then the four waves in order) and
 // writes one partial; one workgroup per camera then sums that camera's partials in a fixed order and applies the
 // finisher.  Translation terms of a photometric loss cancel heavily over up to 10^6 pairs -- hence double.
 #include "common.h"
+#include "project_common.h"
 
-#define SH_C0 0.2820947917738781f
-#define SH_C1 0.48860251190292f
 #define POSE_VALS 15   // v_R (9, row-major), v_t (3), v_campos (3)
 
 // Sum of v over the 256 threads of a workgroup, in a fixed order; the result is in red[0 .. POSE_VALS) after the call.
-// red: 4 * POSE_VALS doubles of LDS.
+// red: 5 * POSE_VALS doubles of LDS.
 __device__ __forceinline__ void block_sum_pose(double (&v)[POSE_VALS], double* red) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < POSE_VALS; ++k) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_xor(v[k], off, 64);
-    }
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < POSE_VALS; ++k) red[wv * POSE_VALS + k] = v[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < POSE_VALS) {
-        const int k = threadIdx.x;
-        red[4 * POSE_VALS + k] = ((red[k] + red[POSE_VALS + k]) + red[2 * POSE_VALS + k]) + red[3 * POSE_VALS + k];
-    }
+    const double sum = block_sum_fixed(v, red);
+    if (threadIdx.x < POSE_VALS) red[4 * POSE_VALS + threadIdx.x] = sum;
     __syncthreads();
     if (threadIdx.x < POSE_VALS) red[threadIdx.x] = red[4 * POSE_VALS + threadIdx.x];
     __syncthreads();
@@ -143,22 +130,10 @@ __global__ __launch_bounds__(256) void k_viewmat_bwd_part(
         const float tx = z * fminf(lim_xp, fmaxf(-lim_xn, xr));
         const float ty = z * fminf(lim_yp, fmaxf(-lim_yn, yr));
         const float a = fx * rz, cj = -fx * tx * rz2, b = fy * rz, d = -fy * ty * rz2;
-        // conic -> cov2d
-        const float A = r0.w, B = r1.x, Cc = r1.y;
-        const float vA = g0.w, vB = 0.5f * g1.x, vC = g1.y;
-        const float X00 = A * vA + B * vB, X01 = A * vB + B * vC;
-        const float X10 = B * vA + Cc * vB, X11 = B * vB + Cc * vC;
-        const float G00 = -(X00 * A + X01 * B);
-        const float G01 = -0.5f * ((X00 * B + X01 * Cc) + (X10 * A + X11 * B));
-        const float G11 = -(X10 * B + X11 * Cc);
-        const float GJ00 = G00 * a, GJ01 = G01 * b, GJ02 = G00 * cj + G01 * d;
-        const float GJ10 = G01 * a, GJ11 = G11 * b, GJ12 = G01 * cj + G11 * d;
-        const float vS00 = a * GJ00, vS01 = a * GJ01, vS02 = a * GJ02;
-        const float vS11 = b * GJ11, vS12 = b * GJ12, vS22 = cj * GJ02 + d * GJ12;
-        const float vJ00 = 2.0f * (GJ00 * S00 + GJ01 * S01 + GJ02 * S02);
-        const float vJ02 = 2.0f * (GJ00 * S02 + GJ01 * S12 + GJ02 * S22);
-        const float vJ11 = 2.0f * (GJ10 * S01 + GJ11 * S11 + GJ12 * S12);
-        const float vJ12 = 2.0f * (GJ10 * S02 + GJ11 * S12 + GJ12 * S22);
+        const Sym3 S = {S00, S01, S02, S11, S12, S22};
+        Sym3 vS;
+        float vJ00, vJ02, vJ11, vJ12;
+        conic_chain(r0, r1, g0, g1, a, cj, b, d, S, vS, vJ00, vJ02, vJ11, vJ12);
         const float vm2x = g0.x, vm2y = g0.y;
         float vpx = fx * rz * vm2x;
         float vpy = fy * rz * vm2y;
@@ -169,7 +144,7 @@ __global__ __launch_bounds__(256) void k_viewmat_bwd_part(
         if (y_in) { vpy += -fy * rz2 * vJ12; vpz += 2.0f * fy * y * rz3 * vJ12; }
         else { vpz += fy * ty * rz3 * vJ12; }
         // v_R = v_p m^T + 2 vS (R Sigma),  v_t = v_p
-        const float vSm[9] = {vS00, vS01, vS02, vS01, vS11, vS12, vS02, vS12, vS22};
+        const float vSm[9] = {vS.xx, vS.xy, vS.xz, vS.xy, vS.yy, vS.yz, vS.xz, vS.yz, vS.zz};
         const float vp[3] = {vpx, vpy, vpz}, m[3] = {mx, my, mz};
 #pragma unroll
         for (int i = 0; i < 3; ++i) {

@@ -11,17 +11,11 @@
 // left to right; 1/x and sqrt correctly rounded -- hipcc's default for HIP).
 #include "stages.h"
 #include "tile_rect.h"
-
-#define CAM_STRIDE 32
-// per-camera block in LDS: [0..11] view matrix rows 0..2 (R|t), 12 fx, 13 fy, 14 cx, 15 cy,
-// 16 lim_x_pos, 17 lim_x_neg, 18 lim_y_pos, 19 lim_y_neg, 20..22 camera position
+#include "project_common.h"
 
 __device__ __forceinline__ float dot3f(float a0, float a1, float a2, float b0, float b1, float b2) {
     return (a0 * b0 + a1 * b1) + a2 * b2;
 }
-
-#define SH_C0 0.2820947917738781f
-#define SH_C1 0.48860251190292f
 
 __global__ __launch_bounds__(256) void k_project_sh_fwd(
     int N, int C, const float* __restrict__ means, const float* __restrict__ quats,

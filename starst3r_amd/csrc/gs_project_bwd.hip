@@ -15,13 +15,11 @@
 // same order: bit-identical gradients.
 #include "stages.h"
 #include "blend_common.h"
+#include "project_common.h"
 
-#define CAM_STRIDE 32
 #ifndef GATHER_WIDE_ABOVE
 #define GATHER_WIDE_ABOVE 6   // slots per pair (wave average) above which the slot gather deals its additions by item
 #endif
-#define SH_C0 0.2820947917738781f
-#define SH_C1 0.48860251190292f
 
 template <bool GATHER>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k_project_sh_bwd(
@@ -282,25 +280,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
         const float tx = z * fminf(o[16], fmaxf(-o[17], xr));
         const float ty = z * fminf(o[18], fmaxf(-o[19], yr));
         const float a = fx * rz, cj = -fx * tx * rz2, b = fy * rz, d = -fy * ty * rz2;
-        // conic -> cov2d
-        const float A = r0.w, B = r1.x, Cc = r1.y;
-        const float vA = g0.w, vB = 0.5f * g1.x, vC = g1.y;
-        const float X00 = A * vA + B * vB, X01 = A * vB + B * vC;
-        const float X10 = B * vA + Cc * vB, X11 = B * vB + Cc * vC;
-        const float G00 = -(X00 * A + X01 * B);
-        const float G01 = -0.5f * ((X00 * B + X01 * Cc) + (X10 * A + X11 * B));
-        const float G11 = -(X10 * B + X11 * Cc);
-        // GJ = G * J, J = [[a,0,cj],[0,b,d]]
-        const float GJ00 = G00 * a, GJ01 = G01 * b, GJ02 = G00 * cj + G01 * d;
-        const float GJ10 = G01 * a, GJ11 = G11 * b, GJ12 = G01 * cj + G11 * d;
-        // v_S = J^T G J
-        const float vS00 = a * GJ00, vS01 = a * GJ01, vS02 = a * GJ02;
-        const float vS11 = b * GJ11, vS12 = b * GJ12, vS22 = cj * GJ02 + d * GJ12;
-        // v_J = 2 G J S
-        const float vJ00 = 2.0f * (GJ00 * S00 + GJ01 * S01 + GJ02 * S02);
-        const float vJ02 = 2.0f * (GJ00 * S02 + GJ01 * S12 + GJ02 * S22);
-        const float vJ11 = 2.0f * (GJ10 * S01 + GJ11 * S11 + GJ12 * S12);
-        const float vJ12 = 2.0f * (GJ10 * S02 + GJ11 * S12 + GJ12 * S22);
+        const Sym3 S = {S00, S01, S02, S11, S12, S22};
+        Sym3 vS;
+        float vJ00, vJ02, vJ11, vJ12;
+        conic_chain(r0, r1, g0, g1, a, cj, b, d, S, vS, vJ00, vJ02, vJ11, vJ12);
         const float vm2x = g0.x, vm2y = g0.y;
         float vpx = fx * rz * vm2x;
         float vpy = fy * rz * vm2y;
@@ -315,7 +298,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
         v_mean[2] += R[2] * vpx + R[5] * vpy + R[8] * vpz;
         // v_Sw += R^T vS R   (U = vS * R, then R^T * U; keep the 6 unique entries)
         float U[9];
-        const float vSm[9] = {vS00, vS01, vS02, vS01, vS11, vS12, vS02, vS12, vS22};
+        const float vSm[9] = {vS.xx, vS.xy, vS.xz, vS.xy, vS.yy, vS.yz, vS.xz, vS.yz, vS.zz};
 #pragma unroll
         for (int i = 0; i < 3; ++i)
 #pragma unroll
