@@ -252,6 +252,46 @@ int st3r_loss_depth_prior(st3r_ctx* ctx, void* stream, int C, int height, int wi
 int st3r_ctx_set_depth_prior(st3r_ctx* ctx, const float* gt, const float* depth, const float* weight, int C, int height,
                              int width, float depth_fac);
 
+/* Per-view exposure: an affine colour transform between the render and the loss, for photographs whose exposure and
+ * white balance differ (the `exposure` of the original 3DGS code, `app_opt` of gsplat's trainer).  exposure [C,3,4]
+ * float32, row major: E_c = [A_c | t_c].  rgb, out, v_out, v_rgb [C,H,W,3].
+ * st3r_exposure_fwd: per pixel x = (r,g,b), in float32 and in this order,
+ *   y_j = fmaf(A[j][2], b, fmaf(A[j][1], g, fmaf(A[j][0], r, t[j])))
+ * st3r_exposure_bwd from v_out = d loss / d y (rgb is the forward's INPUT):
+ *   v_rgb_i = A[0][i] v_y_0 + A[1][i] v_y_1 + A[2][i] v_y_2   (float32, that order; v_rgb may equal v_out)
+ *   v_exposure [C,3,4] (written whole): v_A[j][i] = sum_p v_y_j(p) x_i(p),  v_t[j] = sum_p v_y_j(p)
+ * The twelve sums of a view are formed in double from products (double)v_y * (double)x -- per thread, wave butterfly, the
+ * four waves in order, one 12-double partial per (view, workgroup), a finishing launch with one workgroup per view -- and
+ * stored as float32.  No atomics, a fixed order for a given shape: the same inputs give the same bits.  16-byte accesses
+ * when H * W is a multiple of 4 and the image pointers are 16-byte aligned, 4-byte accesses otherwise. */
+int st3r_exposure_fwd(st3r_ctx* ctx, void* stream, int C, int height, int width, const float* rgb, const float* exposure,
+                      float* out);
+int st3r_exposure_bwd(st3r_ctx* ctx, void* stream, int C, int height, int width, const float* rgb, const float* exposure,
+                      const float* v_out, float* v_rgb, float* v_exposure);
+
+/* One Adam step on the exposures, on the device: exposure, m, v [12C] float32 (in/out) from v_exposure [12C]; torch's
+ * formulas in double, bias corrected by the 1-based `step`:  E <- E - lr mhat / (sqrt(vhat) + eps).  mask (may be NULL):
+ * [C] floats, a view with mask[c] == 0 is skipped whole -- E, m, v keep their bits.  Like st3r_adam_step and
+ * st3r_pose_adam_step the update is guarded on the device by the record count of an asynchronous training step still in
+ * flight: a step that outgrew its buffers moves no exposure.  Non-finite gradients are not filtered. */
+int st3r_exposure_adam_step(st3r_ctx* ctx, void* stream, int C, float* exposure, const float* v_exposure, float* m,
+                            float* v, double lr, double beta1, double beta2, double eps, int step, const float* mask);
+
+/* Registers, for the images at `gt` [C,H,W,3], the exposures [C,3,4] to apply and the buffer v_exposure [C,3,4] that
+ * receives their gradient.  From then on st3r_gs_train_fwd_bwd / _step / _step_poses compare y = E x with the ground
+ * truth whenever their ground-truth pointer is `gt` or a whole-view offset into it (view chunks) with the same height and
+ * width: blend forward, st3r_exposure_fwd into scratch of its own (the raw render stays where st3r_ctx_peek(8) finds it),
+ * the loss on y, st3r_exposure_bwd -- which writes the rows of v_exposure that belong to the call's views and turns
+ * d loss / d y into d loss / d x in place --, blend backward: the kernels and the order of the unfused chain, so the same
+ * bits.  A view belongs to one view chunk, which writes that view's row.  The depth prior and the pose gradient are
+ * unchanged and combine with it.  With no registration every call runs exactly the launches it ran before.  The buffers
+ * stay the CALLER's (the exposures are read by every registered call: update them between calls, e.g. with
+ * st3r_exposure_adam_step on the same stream); gt = NULL (or exposure / v_exposure = NULL) clears the registration.
+ * st3r_gs_raster_train ignores it; with a communicator attached the training calls return ST3R_ERR_INVALID while a
+ * registration applies. */
+int st3r_ctx_set_exposure(st3r_ctx* ctx, const float* gt, const float* exposure, float* v_exposure, int C, int height,
+                          int width);
+
 /* fused Adam over the 23 active scalars per gaussian (replaces the 6 torch.optim.Adam of
  * starster/gs.py:37,159-161; sh0 and SH rows 4..23 never receive gradient and are
  * left untouched, their Adam update is exactly 0).  `step` is 1-based. */

@@ -86,6 +86,8 @@ enum ArenaSlot {
     SLOT_DPRIOR_PART, // depth-prior loss (loss_depth.hip): one double partial per (view, workgroup)
     SLOT_DPRIOR_NORM, // the same: n_c = max(sum w_c, 1) of every registered view, computed once per registration
     SLOT_DPRIOR_SUMS, // the same: sum_p w |ED - Z| per view of the fused step
+    SLOT_EXPOSURE_PART, // exposure backward (gs_exposure.hip): one 12-double partial per (view, workgroup)
+    SLOT_EXPOSED,     // fused step with exposures (fused_step.hip): the exposed image y [C,H,W,3] the loss reads (SLOT_RGB keeps the raw render)
     SLOT_COUNT
 };
 
@@ -132,6 +134,8 @@ struct st3r_ctx {
     // depth prior registered by the caller (st3r_ctx_set_depth_prior, loss_depth.hip): caller-owned, valid until cleared;
     // dp_norm_valid: SLOT_DPRIOR_NORM holds the n_c of this registration (computed by the first training call that uses it)
     const float* dp_gt; const float* dp_depth; const float* dp_weight; int dp_c, dp_h, dp_w; float dp_fac; int dp_norm_valid;
+    // exposures registered by the caller (st3r_ctx_set_exposure, gs_exposure.hip): caller-owned, valid until cleared
+    const float* ex_gt; const float* ex_exposure; float* ex_v_exposure; int ex_c, ex_h, ex_w;
     int bwd_stamp;  // generation stamp of the per-(record, tile) partial-gradient slots
     int depth_stamp;  // the same for the depth backward's slots (SLOT_VTILE_DEPTH)
     uint32_t scan_gen;   // single-pass scan (gs_isect.hip): generation of its status words

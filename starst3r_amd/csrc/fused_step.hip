@@ -238,22 +238,27 @@ struct ViewBatch {
     double* sums;         // [C,2]: L1 and SSIM sums
     double* dp_sums;      // [C]: sum_p w |ED - Z|
     float* v_viewmats;    // [C,4,4]
+    bool exposure;        // exposures may be registered for these views (st3r_ctx_set_exposure)
     ViewBatch slice(int c0, int c1) const {
         return {v.slice(c0, c1), gt + (int64_t)c0 * v.H * v.W * 3, sums + 2 * c0, dp_sums ? dp_sums + c0 : nullptr,
-                v_viewmats ? v_viewmats + 16 * c0 : nullptr};
+                v_viewmats ? v_viewmats + 16 * c0 : nullptr, exposure};
     }
 };
 
-// the images of a step, in ctx scratch (depth, v_depth, v_alpha: with a depth prior only)
-struct StepImages { float *rgb, *alpha; int32_t* last; float *v_rgb, *depth, *v_depth, *v_alpha; };
+// the images of a step, in ctx scratch (depth, v_depth, v_alpha: with a depth prior only; exposed: with exposures only)
+struct StepImages { float *rgb, *alpha; int32_t* last; float *v_rgb, *depth, *v_depth, *v_alpha, *exposed; };
 
-static int step_images(st3r_ctx* ctx, const RasterOut& ro, bool with_depth, StepImages* im) {
+static int step_images(st3r_ctx* ctx, const RasterOut& ro, bool with_depth, bool with_exposure, StepImages* im) {
     const int64_t n_px = (int64_t)ro.C * ro.H * ro.W;
     ARENA_GET(SLOT_RGB, float, n_px * 3, rgb);
     ARENA_GET(SLOT_ALPHA, float, n_px, alpha);
     ARENA_GET(SLOT_LAST, int32_t, n_px, last);
     ARENA_GET(SLOT_VRENDER, float, n_px * 3, v_rgb);
-    *im = StepImages{rgb, alpha, last, v_rgb, nullptr, nullptr, nullptr};
+    *im = StepImages{rgb, alpha, last, v_rgb, nullptr, nullptr, nullptr, nullptr};
+    if (with_exposure) {
+        ARENA_GET(SLOT_EXPOSED, float, n_px * 3, exposed);
+        im->exposed = exposed;
+    }
     if (with_depth) {
         ARENA_GET(SLOT_DEPTH, float, n_px, depth);
         ARENA_GET(SLOT_VDEPTH, float, n_px, v_depth);
@@ -267,7 +272,9 @@ static int step_images(st3r_ctx* ctx, const RasterOut& ro, bool with_depth, Step
 // dp.prior != NULL: the step also renders the depth map of the same lists and takes the prior's loss, which sends v_D
 // and v_alpha back.
 static int forward_and_losses(st3r_ctx* ctx, hipStream_t s, const RasterOut& ro, const ViewBatch& b, float ssim_fac,
-                              bool sums_cleared, const DepthPrior& dp, const StepImages& im) {
+                              bool sums_cleared, const DepthPrior& dp, const ExposureReg& ex, const StepImages& im) {
+    // ex.exposure != NULL: the loss compares y = E x with the ground truth (the stand-alone kernels of gs_exposure.hip, in
+    // the order of the unfused chain); im.v_rgb leaves as d loss / d x, ex.v_exposure as d loss / d E of these views
     const bool eio = true;   // the fused path's offsets table carries the total as its last entry
     st3r_prof_begin(ctx, s, STG_BLEND_FWD);
     int rc = st3r_blend_fwd_impl(ctx, s, ro, im.rgb, im.alpha, im.last, true, eio);
@@ -275,7 +282,12 @@ static int forward_and_losses(st3r_ctx* ctx, hipStream_t s, const RasterOut& ro,
     st3r_prof_end(ctx, s, STG_BLEND_FWD);
     if (rc) return rc;
     st3r_prof_begin(ctx, s, STG_LOSS);
-    rc = st3r_loss_impl(ctx, s, ro.C, ro.H, ro.W, im.rgb, b.gt, 1.0f - ssim_fac, ssim_fac, b.sums, im.v_rgb, sums_cleared);
+    if (ex.exposure) rc = st3r_exposure_fwd_impl(s, ro.C, ro.H, ro.W, im.rgb, ex.exposure, im.exposed);
+    if (!rc)
+        rc = st3r_loss_impl(ctx, s, ro.C, ro.H, ro.W, ex.exposure ? im.exposed : im.rgb, b.gt, 1.0f - ssim_fac, ssim_fac,
+                            b.sums, im.v_rgb, sums_cleared);
+    if (!rc && ex.exposure)
+        rc = st3r_exposure_bwd_impl(ctx, s, ro.C, ro.H, ro.W, im.rgb, ex.exposure, im.v_rgb, im.v_rgb, ex.v_exposure);
     if (!rc && dp.prior)
         rc = st3r_depth_prior_loss_impl(ctx, s, ro.C, ro.H, ro.W, im.depth, im.alpha, dp.prior, dp.weight, dp.norm, 1, dp.fac,
                                         b.dp_sums, 1, im.v_depth, im.v_alpha);
@@ -354,6 +366,8 @@ static int train_views(st3r_ctx* ctx, hipStream_t s, const GsParams& g, const Vi
     DepthPrior dp{};
     int rc = b.dp_sums ? st3r_depth_prior_for(ctx, s, b.gt, v.C, v.H, v.W, &dp) : ST3R_OK;
     if (rc) return rc;
+    ExposureReg ex{};
+    if (b.exposure) st3r_exposure_for(ctx, b.gt, v.C, v.H, v.W, &ex);
     // The one decision: with a depth prior the projection backward reads the per-pair array v_pairs (colour + depth
     // gradients, added), without one it sums the colour backward's slots itself.
     const bool need_pairs = dp.prior != nullptr;
@@ -361,14 +375,14 @@ static int train_views(st3r_ctx* ctx, hipStream_t s, const GsParams& g, const Vi
     rc = rasterize_front(ctx, s, g, v, reg_sums, 1, nullptr, allow_async, &ro, b.sums);
     if (rc) return rc;
     StepImages im;
-    rc = step_images(ctx, ro, need_pairs, &im);
+    rc = step_images(ctx, ro, need_pairs, ex.exposure != nullptr, &im);
     if (rc) return rc;
     float* v_pairs = nullptr;   // per-pair gradients [N*C, 12]: the projection backward's input and / or the pose backward's
     if (need_pairs || b.v_viewmats) {
         ARENA_GET(SLOT_VSPLATS, float, ro.n_pairs * ST3R_SPLAT_STRIDE, vp);
         v_pairs = vp;
     }
-    rc = forward_and_losses(ctx, s, ro, b, f.ssim, true, dp, im);
+    rc = forward_and_losses(ctx, s, ro, b, f.ssim, true, dp, ex, im);
     if (rc) return rc;
     st3r_vtile_ref slots{};
     rc = blend_backward(ctx, s, ro, im, need_pairs, &slots, v_pairs);
@@ -448,6 +462,14 @@ int st3r_train_fwd_bwd_impl(st3r_ctx* ctx, hipStream_t s, const GsParams& g, con
         ARENA_GET(SLOT_DPRIOR_SUMS, double, (size_t)C, ds);
         dp_sums = ds;
     }
+    // exposures registered for these views (st3r_ctx_set_exposure): the depth prior's rule under a communicator
+    ExposureReg ex;
+    st3r_exposure_for(ctx, gt_images, C, v.H, v.W, &ex);
+    if (ex.exposure && ctx->comm) {
+        st3r_set_error("exposures are registered and a communicator is attached -- per-view exposures are not supported "
+                       "in view-sharded training (clear them with st3r_ctx_set_exposure(ctx, NULL, ...))");
+        return ST3R_ERR_INVALID;
+    }
     st3r_prof_next_step(ctx);
     rc = st3r_count_settle(ctx);
     if (rc) return rc;
@@ -456,7 +478,8 @@ int st3r_train_fwd_bwd_impl(st3r_ctx* ctx, hipStream_t s, const GsParams& g, con
     if ((ctx->debug_flags & 32) && chunks < 2) chunks = 2;
     if (chunks > C) chunks = C;
     int64_t stats[3];
-    rc = train_chunks(ctx, s, g, ViewBatch{v, gt_images, sums, dp_sums, v_viewmats}, LossFacs{ssim_fac, opac_fac, scale_fac},
+    rc = train_chunks(ctx, s, g, ViewBatch{v, gt_images, sums, dp_sums, v_viewmats, ex.exposure != nullptr},
+                      LossFacs{ssim_fac, opac_fac, scale_fac},
                       reg_sums, reg_sums + 4, stats_host != nullptr, grads, &chunks, stats);
     if (rc) return rc;
     if (chunks > 1) ctx->view_chunks = chunks;
@@ -492,7 +515,7 @@ ST3R_EXPORT int st3r_gs_raster_train(st3r_ctx* ctx, void* stream, int N, int C, 
     hipStream_t s = (hipStream_t)stream;
     ARENA_GET(SLOT_SMALL, double, 2 * (size_t)C + 8, sums);
     double* reg_sums = sums + 2 * C;
-    const ViewBatch b{GsViews{C, width, height}, gt_images, sums, nullptr, nullptr};   // (no camera is looked at)
+    const ViewBatch b{GsViews{C, width, height}, gt_images, sums, nullptr, nullptr, false};   // (no camera is looked at)
     HIP_TRY(hipMemsetAsync(reg_sums, 0, sizeof(double) * 4, s));  // stays zero: the regularisers belong to the owners
     st3r_prof_next_step(ctx);
     RasterOut ro;
@@ -502,9 +525,9 @@ ST3R_EXPORT int st3r_gs_raster_train(st3r_ctx* ctx, void* stream, int N, int C, 
     if (rc == ST3R_SPLIT_VIEWS) rc = ST3R_ERR_INVALID;
     if (rc) return rc;
     StepImages im;
-    rc = step_images(ctx, ro, false, &im);
+    rc = step_images(ctx, ro, false, false, &im);
     if (rc) return rc;
-    rc = forward_and_losses(ctx, s, ro, b, ssim_fac, false, DepthPrior{}, im);
+    rc = forward_and_losses(ctx, s, ro, b, ssim_fac, false, DepthPrior{}, ExposureReg{}, im);
     if (rc) return rc;
     st3r_prof_begin(ctx, s, STG_BLEND_BWD);
     rc = st3r_blend_bwd_impl(ctx, s, ro, im.alpha, im.last, im.v_rgb, nullptr, v_records, true, nullptr);

@@ -116,7 +116,8 @@ __global__ __launch_bounds__(DP_T) void k_dprior_loss(int64_t HW, int64_t chunk,
 
 // workgroups per view and pixels per workgroup: at least four pixels per thread, at most 256 x 8 workgroups in all (one
 // resident round of the chip; the count is C times a per-view count, so it is not an exact multiple of 256)
-static void dp_grid(int C, int64_t HW, int* blocks, int64_t* chunk) {
+// (stages.h: gs_exposure.hip deals its pixels the same way)
+void st3r_stream_grid(int C, int64_t HW, int* blocks, int64_t* chunk) {
     int64_t want = (C * HW + DP_ALIGN - 1) / DP_ALIGN;
     if (want > 256 * 8) want = 256 * 8;
     int64_t b = want / C;
@@ -138,7 +139,7 @@ static int dp_partials(st3r_ctx* ctx, int C, int blocks, double** part) {
 // norm[c * stride] = n_c of the views at `weight`
 static int dp_norms(st3r_ctx* ctx, hipStream_t s, int C, int64_t HW, const float* weight, double* norm, int stride) {
     int blocks; int64_t chunk;
-    dp_grid(C, HW, &blocks, &chunk);
+    st3r_stream_grid(C, HW, &blocks, &chunk);
     double* part;
     int rc = dp_partials(ctx, C, blocks, &part);
     if (rc) return rc;
@@ -158,7 +159,7 @@ int st3r_depth_prior_loss_impl(st3r_ctx* ctx, hipStream_t s, int C, int H, int W
                                float depth_fac, double* sums, int sums_stride, float* v_depth, float* v_alpha) {
     const int64_t HW = (int64_t)H * W;
     int blocks; int64_t chunk;
-    dp_grid(C, HW, &blocks, &chunk);
+    st3r_stream_grid(C, HW, &blocks, &chunk);
     double* part;
     int rc = dp_partials(ctx, C, blocks, &part);
     if (rc) return rc;

@@ -42,6 +42,9 @@ static inline RasterOut stage_lists(int C, int W, int H, int tile_w, int tile_h,
 // the registered depth prior of a set of views (loss_depth.hip); prior == NULL: none applies
 struct DepthPrior { const float* prior; const float* weight; const double* norm; float fac; };
 
+// the registered exposures of a set of views (gs_exposure.hip) and where their gradient goes; exposure == NULL: none applies
+struct ExposureReg { const float* exposure; float* v_exposure; };
+
 // ---- api.hip, fused_step.hip, comm.hip ----
 // The 16 device words next to the fused steps: [0] record count of an asynchronous step (k_adam compares it with the
 // step's capacity), [4] status word of an exchanged step (comm.hip).  Zeroed when allocated.
@@ -102,10 +105,19 @@ int st3r_add_pairs_impl(hipStream_t s, int64_t n_pairs, float* a, const float* b
 // ---- loss.hip, loss_depth.hip ----
 int st3r_loss_impl(st3r_ctx* ctx, hipStream_t s, int C, int H, int W, const float* render, const float* gt,
                    float w_l1, float w_ssim, double* sums, float* v_render, bool sums_cleared);
+// how the streaming per-view kernels (k_dprior_loss, k_exposure_fwd / _bwd) deal HW pixels of C views to workgroups of 256
+// threads: contiguous chunks of a multiple of 1024 pixels, at most 2048 workgroups in all
+void st3r_stream_grid(int C, int64_t HW, int* blocks, int64_t* chunk);
 int st3r_depth_prior_for(st3r_ctx* ctx, hipStream_t s, const float* gt, int C, int H, int W, DepthPrior* out);
 int st3r_depth_prior_loss_impl(st3r_ctx* ctx, hipStream_t s, int C, int H, int W, const float* depth, const float* alpha,
                                const float* prior, const float* weight, const double* norm, int norm_stride,
                                float depth_fac, double* sums, int sums_stride, float* v_depth, float* v_alpha);
+
+// ---- gs_exposure.hip ----
+void st3r_exposure_for(st3r_ctx* ctx, const float* gt, int C, int H, int W, ExposureReg* out);
+int st3r_exposure_fwd_impl(hipStream_t s, int C, int H, int W, const float* rgb, const float* exposure, float* out);
+int st3r_exposure_bwd_impl(st3r_ctx* ctx, hipStream_t s, int C, int H, int W, const float* rgb, const float* exposure,
+                           const float* v_out, float* v_rgb, float* v_exposure);
 
 // ---- adam.hip ----
 // i0 < 0: the whole buffer.  [g0, g1) a proper sub-range of the Gaussians: that range instead of [i0, i1).

@@ -275,35 +275,77 @@ class _RasterizeDepth(torch.autograd.Function):
         return G["means"], G["quats"], G["scales"], G["opacities"], v_sh, v_w2c, None, None, None, None
 
 
-def render_3dgs(scene, w2c: torch.Tensor, intrinsics: torch.Tensor, width: int, height: int, render_mode: str = "RGB"):
+class _Exposure(torch.autograd.Function):
+    """y = A x + t per view (st3r_exposure_fwd / st3r_exposure_bwd): differentiable into the render and the exposures."""
+
+    @staticmethod
+    def forward(fctx, rgb, exposure, ctx):
+        rgb, exposure = rgb.contiguous(), exposure.contiguous()
+        fctx.save_for_backward(rgb, exposure)
+        fctx.ctx = ctx
+        return ops.exposure_fwd(ctx, rgb, exposure)
+
+    @staticmethod
+    def backward(fctx, v_out):
+        rgb, exposure = fctx.saved_tensors
+        v_rgb, v_exposure = ops.exposure_bwd(fctx.ctx, rgb, exposure, v_out.contiguous().float())
+        return v_rgb, v_exposure, None
+
+
+def _check_render_exposure(exposure, n_views, render_mode):
+    """the checks of render_3dgs(exposure=...), before anything runs"""
+    if render_mode in ("D", "ED"):
+        raise ValueError(f"exposure applies to the RGB channels: render_mode {render_mode!r} has none")
+    if not torch.is_tensor(exposure) or tuple(exposure.shape) != (n_views, 3, 4):
+        shape = tuple(exposure.shape) if torch.is_tensor(exposure) else type(exposure).__name__
+        raise ValueError(f"exposure must be a tensor of shape ({n_views}, 3, 4), one [A | t] per view, got {shape}")
+
+
+def render_3dgs(scene, w2c: torch.Tensor, intrinsics: torch.Tensor, width: int, height: int, render_mode: str = "RGB",
+                exposure=None):
     """Render the splats from a set of camera views (reference gs.py:47-88).
 
     Returns the tuple the reference gets from gsplat.rasterization: (render_img (N,H,W,3),
     render_alpha (N,H,W,1), info).  render_mode follows gsplat: "D" (accumulated depth sum_i w_i z_i) and "ED"
     (expected depth D / clamp(alpha, min=1e-10)) return render_img (N,H,W,1); "RGB+D" and "RGB+ED" return (N,H,W,4)
-    with the depth last.  Every mode back-propagates into the Gaussians and, when it requires a gradient, into w2c."""
+    with the depth last.  Every mode back-propagates into the Gaussians and, when it requires a gradient, into w2c.
+    exposure (not in the reference): a (N,3,4) tensor, one affine colour transform [A | t] per view, applied to the RGB
+    channels of render_img (y = A x + t); differentiable into the Gaussians, w2c and exposure."""
     if render_mode not in RENDER_MODES:
         raise ValueError(f"render_mode must be one of {RENDER_MODES}, got {render_mode!r}")
+    if exposure is not None:
+        _check_render_exposure(exposure, w2c.shape[0], render_mode)
     g = scene.gaussians
     ctx = ops.get_context(scene.device)
     w2c = w2c.to(scene.device, torch.float32).contiguous(); Ks = intrinsics.to(scene.device, torch.float32).contiguous()
+    if exposure is not None:
+        exposure = exposure.to(scene.device, torch.float32)
     if render_mode == "RGB":
         rgb, alpha = _Rasterize.apply(g["means"], g["quats"], g["scales"], g["opacities"], g["shN"], w2c, Ks, width,
                                       height, ctx)
-        img = rgb
+        img = rgb if exposure is None else _Exposure.apply(rgb, exposure, ctx)
     else:
         rgb, alpha, depth = _RasterizeDepth.apply(g["means"], g["quats"], g["scales"], g["opacities"], g["shN"], w2c, Ks,
                                                   width, height, ctx)
         if render_mode.endswith("ED"):
             depth = depth / alpha.clamp(min=1e-10)
+        if exposure is not None and render_mode.startswith("RGB"):
+            rgb = _Exposure.apply(rgb, exposure, ctx)
         img = torch.cat([rgb, depth], dim=-1) if render_mode.startswith("RGB") else depth
     # the info dict of the most recent rasterization (gsplat's `meta`)
     info = {k: v for k, v in ops.last_info().items() if not k.startswith("_")}
     return img, alpha, info
 
 
-def render_3dgs_original(scene, width: int, height: int, render_mode: str = "RGB"):
-    """Render from camera views of original scene (reference gs.py:90-95)."""
+def render_3dgs_original(scene, width: int, height: int, render_mode: str = "RGB", exposure=False):
+    """Render from camera views of original scene (reference gs.py:90-95).  exposure=True (not in the reference): through
+    the trained scene.exposures (run_3dgs_optim(exposure_lr=...)), i.e. as the photographs were taken."""
+    if exposure:
+        E = getattr(scene, "exposures", None)
+        if E is None:
+            raise ValueError("exposure=True needs trained exposures: scene.exposures does not exist "
+                             "(run_3dgs_optim(exposure_lr=...) creates it)")
+        return scene.render_3dgs(scene.w2c, scene.intrinsics, width, height, render_mode=render_mode, exposure=E)
     if render_mode == "RGB":
         return scene.render_3dgs(scene.w2c, scene.intrinsics, width, height)
     return scene.render_3dgs(scene.w2c, scene.intrinsics, width, height, render_mode=render_mode)
@@ -355,6 +397,16 @@ def _depth_prior_on_device(scene, views, conf_thres, height, width):
     return scene._depth_dev[1], scene._depth_dev[2]
 
 
+def _exposure_frozen(n_views, exposure_freeze):
+    """sorted view indices of exposure_freeze (negative ones count from the end); ValueError outside [-n_views, n_views)"""
+    out = set()
+    for i in exposure_freeze:
+        if isinstance(i, bool) or int(i) != i or not -n_views <= int(i) < n_views:
+            raise ValueError(f"exposure_freeze holds {i!r}: not the index of one of the {n_views} views")
+        out.add(int(i) % n_views)
+    return sorted(out)
+
+
 def run_3dgs_optim(
         scene,
         iters: int,
@@ -367,6 +419,8 @@ def run_3dgs_optim(
         pose_freeze=(),
         depth_fac=0.0,
         depth_conf_thres=1.5,
+        exposure_lr=0.0,
+        exposure_freeze=(),
     ) -> list:
     """Run 3DGS optimization and pruning (optional) for a number of iterations (reference gs.py:97-166).
 
@@ -388,6 +442,17 @@ def run_3dgs_optim(
     map in scene.depth_maps (Scene.add_images keeps the alignment's; they are in the gauge of the poses, so nothing is
     fitted) and w = 1 where scene.depth_confs exceeds depth_conf_thres, else 0 (all ones when depth_confs is empty).  Works
     together with pose_lr and enable_pruning; single process, Gaussians replicated only.
+
+    exposure_lr (not in the reference; a float or a callable step -> float as pose_lr): when not 0.0 every view gets an
+    affine colour transform y = A x + t between its render and the loss, inside the same fused step, trained by its own
+    Adam (the Gaussians' betas and eps) from the identity: photographs taken with auto-exposure and auto-white-balance
+    disagree photometrically, and without it the Gaussians explain that with view-dependent colour and floaters.  The
+    transforms live in scene.exposures [len(scene.imgs),3,4] (float32, on the device; created as identities on first use or
+    when the number of images changed) and are trained in place; their moments and step counter persist on
+    scene._gs_optim (exp_m, exp_v, exp_step).  The views in exposure_freeze keep their exposure bit for bit: they fix the
+    gauge between colours and exposures.  render_3dgs_original(exposure=True) renders through them.  Works together with
+    pose_lr, depth_fac and enable_pruning; single process, Gaussians replicated only.  With exposure_lr == 0 nothing about
+    the call changes and scene.exposures is not created.
     """
     poses_on = callable(pose_lr) or float(pose_lr) != 0.0
     depth_on = float(depth_fac) != 0.0
@@ -397,6 +462,12 @@ def run_3dgs_optim(
     if poses_on and (_dist.rank_world()[1] > 1 or _sharded_layout(scene, 1, enable_pruning)):
         raise NotImplementedError("pose_lr != 0 is supported in a single process with replicated Gaussians only "
                                   "(not under torch.distributed, not with ST3R_MULTI_GPU=gaussian-sharded)")
+    exposure_on = callable(exposure_lr) or float(exposure_lr) != 0.0
+    if exposure_on and (_dist.rank_world()[1] > 1 or _sharded_layout(scene, 1, enable_pruning)):
+        raise NotImplementedError("exposure_lr != 0 is supported in a single process with replicated Gaussians only "
+                                  "(not under torch.distributed, not with ST3R_MULTI_GPU=gaussian-sharded)")
+    if exposure_on:   # (checked before anything runs)
+        exp_frozen = _exposure_frozen(len(scene.imgs), exposure_freeze)
     height, width = scene.imgs[0].shape[:2]
     ctx = ops.get_context(scene.device)
     st = scene._gs_optim
@@ -427,6 +498,21 @@ def run_3dgs_optim(
         if frozen:
             pose_mask[frozen] = 0.0
         st.pose_w2c = w2c   # the matrices being trained (diagnostics; scene.c2w follows when the loop ends)
+    if exposure_on:
+        n_img = len(scene.imgs)
+        E = getattr(scene, "exposures", None)
+        if E is None or tuple(E.shape) != (n_img, 3, 4):   # first use, or the number of images changed
+            E = torch.eye(3, 4, device=gt.device).repeat(n_img, 1, 1)
+        if E.dtype != torch.float32 or E.device != gt.device or not E.is_contiguous():
+            E = E.detach().to(gt.device, torch.float32).contiguous()
+        scene.exposures = E   # trained in place
+        if getattr(st, "exp_m", None) is None or st.exp_m.numel() != 12 * n_img:
+            st.exp_m = torch.zeros(12 * n_img, device=gt.device); st.exp_v = torch.zeros_like(st.exp_m)
+            st.exp_step = 0
+        st.exp_grad = torch.zeros((n_img, 3, 4), device=gt.device)   # this step's d loss / d exposures (diagnostics)
+        exp_mask = torch.ones(n_img, device=gt.device)
+        if exp_frozen:
+            exp_mask[exp_frozen] = 0.0
     restore_exchange = None
     if enable_pruning and fused and world > 1 and ops.get_exchange(ctx) in ("rs_ag", "direct"):
         # reduce-scatter exchange (through RCCL or through the peers' exported buffers): a rank maintains the Adam moments of its piece of the buffer only; growing the set
@@ -470,6 +556,10 @@ def run_3dgs_optim(
                               loss_scale_fac, st.grads, losses[step:step + 1], want_stats=True)
             _dist.all_reduce_sum(st.grads)
             ops.adam_step(ctx, P, st.grads, st.m, st.v, st.lr, st.betas[0], st.betas[1], st.eps, st.step)
+        if exposure_on:   # behind the step on the same stream, and behind the same device-side guard as its updates
+            ops.exposure_adam_step(ctx, scene.exposures, st.exp_grad, st.exp_m, st.exp_v,
+                                   float(exposure_lr(step)) if callable(exposure_lr) else float(exposure_lr), st.betas[0],
+                                   st.betas[1], st.eps, st.exp_step, exp_mask)
 
     def capacity_error(e):
         return getattr(e, "code", 0) == -3 and world == 1
@@ -478,6 +568,8 @@ def run_3dgs_optim(
         st.step += d
         if poses_on:
             st.pose_step += d
+        if exposure_on:
+            st.exp_step += d
 
     # A peer failure (ST3R_ERR_PEER: the step before failed on some rank, nobody applied it) ABORTS the run on every rank
     # alike -- all ranks get the code from the same call --; the exchange form is restored whatever ends the loop.
@@ -488,6 +580,8 @@ def run_3dgs_optim(
     try:
         if depth_on:   # the prior belongs to this call: cleared below whatever ends the loop
             ops.set_depth_prior(ctx, gt, prior, prior_w, float(depth_fac))
+        if exposure_on:   # and so do the exposures
+            ops.set_exposure(ctx, gt, scene.exposures, st.exp_grad)
         step = 0
         for _ in it_range:
             if enable_pruning:
@@ -536,6 +630,8 @@ def run_3dgs_optim(
         ops.set_gt_moments(ctx, None, None)
         if depth_on:
             ops.set_depth_prior(ctx, None, None, None)
+        if exposure_on:
+            ops.set_exposure(ctx, None, None, None)
         if sh_c[0].shape[0] == g["shN"].shape[0]:
             sh_write_back()
         if restore_exchange is not None:   # (the moments stay complete on every rank: rs_ag goes on using its own piece)

@@ -310,6 +310,58 @@ def set_depth_prior(ctx, gt, depth, weight, depth_fac=1.0):
     ctx._dp_keep = (gt, depth, weight)
 
 
+def _exposure_shapes(rgb, exposure):
+    if rgb.dim() != 4 or rgb.shape[-1] != 3 or tuple(exposure.shape) != (rgb.shape[0], 3, 4):
+        raise ValueError(f"expected images [C,H,W,3] and exposures [C,3,4], got {tuple(rgb.shape)} and "
+                         f"{tuple(exposure.shape)}")
+    return rgb.shape[0], rgb.shape[1], rgb.shape[2]
+
+
+def exposure_fwd(ctx, rgb, exposure, out=None):
+    """y = A x + t per pixel of rgb [C,H,W,3] with the view's exposure [C,3,4] = [A | t] (st3r_exposure_fwd)."""
+    Cn, H, W = _exposure_shapes(rgb, exposure)
+    out = torch.empty_like(rgb) if out is None else out
+    _lib.check(_lib.lib().st3r_exposure_fwd(ctx.handle, _stream(), Cn, H, W, _p(rgb), _p(exposure), _p(out)))
+    return out
+
+
+def exposure_bwd(ctx, rgb, exposure, v_out, v_rgb=None, v_exposure=None):
+    """Backward of exposure_fwd from v_out = d loss / d y; rgb is the forward's input.  Returns (v_rgb [C,H,W,3],
+    v_exposure [C,3,4]); v_rgb may be v_out itself (in place) (st3r_exposure_bwd)."""
+    Cn, H, W = _exposure_shapes(rgb, exposure)
+    if v_out.shape != rgb.shape:
+        raise ValueError(f"v_out has shape {tuple(v_out.shape)}, the images {tuple(rgb.shape)}")
+    v_rgb = torch.empty_like(rgb) if v_rgb is None else v_rgb
+    v_exposure = torch.empty_like(exposure) if v_exposure is None else v_exposure
+    _lib.check(_lib.lib().st3r_exposure_bwd(ctx.handle, _stream(), Cn, H, W, _p(rgb), _p(exposure), _p(v_out), _p(v_rgb),
+                                            _p(v_exposure)))
+    return v_rgb, v_exposure
+
+
+def exposure_adam_step(ctx, exposure, v_exposure, m, v, lr, b1, b2, eps, step, mask=None):
+    """One Adam step on the exposures [C,3,4], in place, from v_exposure [C,3,4]; moments m / v [12C]
+    (st3r_exposure_adam_step).  mask [C] floats or None: views with mask == 0 keep every bit."""
+    Cn = exposure.shape[0]
+    assert exposure.numel() == 12 * Cn and v_exposure.numel() == 12 * Cn and m.numel() == 12 * Cn and v.numel() == 12 * Cn
+    _lib.check(_lib.lib().st3r_exposure_adam_step(ctx.handle, _stream(), Cn, _p(exposure), _p(v_exposure), _p(m), _p(v), lr,
+                                                  b1, b2, eps, step, _p(mask)))
+
+
+def set_exposure(ctx, gt, exposure, v_exposure):
+    """Register the exposures [C,3,4] of the images gt [C,H,W,3] and the buffer v_exposure [C,3,4] that receives their
+    gradient -- train_fwd_bwd, train_step and train_step_poses on `gt` (or whole views of it) then compare the exposed
+    render with the ground truth and write v_exposure (st3r_ctx_set_exposure) -- or clear the registration (gt = None).
+    The caller's tensors are kept alive here."""
+    if gt is None or exposure is None or v_exposure is None:
+        _lib.check(_lib.lib().st3r_ctx_set_exposure(ctx.handle, None, None, None, 0, 0, 0))
+        ctx._ex_keep = None
+        return
+    assert gt.is_contiguous() and tuple(exposure.shape) == (gt.shape[0], 3, 4) and v_exposure.shape == exposure.shape
+    _lib.check(_lib.lib().st3r_ctx_set_exposure(ctx.handle, _p(gt), _p(exposure), _p(v_exposure), gt.shape[0], gt.shape[1],
+                                                gt.shape[2]))
+    ctx._ex_keep = (gt, exposure, v_exposure)
+
+
 def adam_step(ctx, params, grads, m, v, lr, b1, b2, eps, step):
     """params: dict with means, quats, scales, opacities, shN (updated in place)."""
     N = params["means"].shape[0]

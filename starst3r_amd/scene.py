@@ -90,20 +90,29 @@ class Scene:
     def init_3dgs(self, init_scale=3e-3, lr=1e-3):
         _gs.init_3dgs(self, init_scale, lr)
 
-    def render_3dgs(self, w2c, intrinsics, width, height, render_mode="RGB"):
+    def render_3dgs(self, w2c, intrinsics, width, height, render_mode="RGB", exposure=None):
+        if exposure is not None:
+            return _gs.render_3dgs(self, w2c, intrinsics, width, height, render_mode=render_mode, exposure=exposure)
         if render_mode == "RGB":   # the reference's call, argument for argument
             return _gs.render_3dgs(self, w2c, intrinsics, width, height)
         return _gs.render_3dgs(self, w2c, intrinsics, width, height, render_mode=render_mode)
 
-    def render_3dgs_original(self, width, height, render_mode="RGB"):
+    def render_3dgs_original(self, width, height, render_mode="RGB", exposure=False):
+        if exposure:
+            return _gs.render_3dgs_original(self, width, height, render_mode=render_mode, exposure=True)
         if render_mode == "RGB":
             return _gs.render_3dgs_original(self, width, height)
         return _gs.render_3dgs_original(self, width, height, render_mode=render_mode)
 
     def run_3dgs_optim(self, iters: int, enable_pruning: bool = False, loss_ssim_fac=0.2, loss_opacity_fac=0.01,
                        loss_scale_fac=0.01, verbose: bool = False, pose_lr=0.0, pose_freeze=(), depth_fac=0.0,
-                       depth_conf_thres=1.5) -> list:
+                       depth_conf_thres=1.5, exposure_lr=0.0, exposure_freeze=()) -> list:
         poses_off = not callable(pose_lr) and float(pose_lr) == 0.0 and not tuple(pose_freeze)
+        if callable(exposure_lr) or float(exposure_lr) != 0.0:
+            return _gs.run_3dgs_optim(self, iters, enable_pruning, loss_ssim_fac, loss_opacity_fac, loss_scale_fac,
+                                      verbose, pose_lr=pose_lr, pose_freeze=pose_freeze, depth_fac=depth_fac,
+                                      depth_conf_thres=depth_conf_thres, exposure_lr=exposure_lr,
+                                      exposure_freeze=exposure_freeze)
         if float(depth_fac) != 0.0:
             return _gs.run_3dgs_optim(self, iters, enable_pruning, loss_ssim_fac, loss_opacity_fac, loss_scale_fac,
                                       verbose, pose_lr=pose_lr, pose_freeze=pose_freeze, depth_fac=depth_fac,
