@@ -7,7 +7,7 @@
 // grads / m / v use the block layout means[3N] quats[4N] scales[3N] opacities[N] sh4[12N];
 // parameters are updated in place in the caller's tensors (sh with row stride sh_stride).
 // Arithmetic mirrors torch.optim.Adam's single-tensor path (see oracle/gs_oracle.c gso_adam).
-#include "stages.h"
+#include "per_view.h"   // aligned16
 
 struct AdamK {
     float step_size, bc2_sqrt, w1, w2, b2, eps;
@@ -178,11 +178,10 @@ int st3r_adam_impl(hipStream_t s, int N, float* means, float* quats, float* scal
     const AdamK k = adam_constants(lr, b1, b2, eps, step);
     const int64_t total = (g1 - g0 < N) ? 23 * (g1 - g0) : i1 - i0;
     if (total <= 0) return ST3R_OK;
-    auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
     const bool contiguous = !(g1 - g0 < N) && !gstage;
 #ifndef ADAM_NO_VEC
-    if (contiguous && N % 4 == 0 && i0 % 4 == 0 && (i1 - i0) % 4 == 0 && sh_stride % 4 == 0 && al16(means) && al16(quats) &&
-        al16(scales) && al16(opacities) && al16(sh) && al16(grads) && al16(m) && al16(v) && (!pstage || al16(pstage))) {
+    if (contiguous && N % 4 == 0 && i0 % 4 == 0 && (i1 - i0) % 4 == 0 && sh_stride % 4 == 0 &&
+        aligned16(means, quats, scales, opacities, sh, grads, m, v, pstage)) {
         int blocks4 = ceil_div(total / 4, 256);
         if (blocks4 > 256 * 16) blocks4 = 256 * 16;
         hipLaunchKernelGGL(k_adam4, dim3(blocks4), dim3(256), 0, s, (int64_t)N, means, quats, scales, opacities, sh,

@@ -116,6 +116,28 @@ enum Stage {
 // written by k_blend_bwd for scenes of many slots per pair, so that the gather can skip the slots of pairs nobody touched
 struct st3r_vtile_ref { const int32_t* cum; const float* vtile; int stamp; unsigned vt_cap; const uint32_t* touch; };
 
+// "Registered for these views": the c images of h x w pixels at gt ([c,h,w,3]); gt == NULL: nothing registered.
+struct ViewReg { const float* gt; int c, h, w; };
+
+// The first registered view of a call on the C views of H x W pixels at `gt`, or -1 when the registration does not
+// apply: nothing registered, another image size, not a whole-view offset into the registered images (a call on a view
+// chunk is one), or more views than are registered.  The one rule that makes view chunks work with every option.
+static inline int64_t view_reg_first(const ViewReg& r, const float* gt, int C, int H, int W) {
+    if (!r.gt || H != r.h || W != r.w) return -1;
+    const int64_t img = (int64_t)H * W * 3;
+    if (gt < r.gt || (gt - r.gt) % img != 0) return -1;
+    const int64_t c0 = (gt - r.gt) / img;
+    return c0 + C <= r.c ? c0 : -1;
+}
+
+// the st3r_ctx_set_* calls: `on` false (a NULL pointer among the caller's) clears *r, otherwise the views are checked and stored
+static inline int view_reg_set(ViewReg* r, bool on, const float* gt, int C, int height, int width) {
+    if (!on) { *r = ViewReg{}; return ST3R_OK; }
+    ARG_CHECK(C > 0 && height > 0 && width > 0);
+    *r = ViewReg{gt, C, height, width};
+    return ST3R_OK;
+}
+
 struct st3r_ctx {
     int device;
     void* slot_ptr[SLOT_COUNT];
@@ -129,13 +151,14 @@ struct st3r_ctx {
                       // st3r_gs_train_step behaves as if this rank's forward / backward had failed (comm.hip)
                       // (round 5's experiment switches -- 4096 masked rectangles, 8192 cell-granular backward, 16384 slot sums
                       // in a kernel of their own -- left the library in round 6: tools/experiments/README.md)
-    // ground-truth moments registered by the caller (st3r_ctx_set_gt_moments, loss.hip): caller-owned, valid until cleared
-    const float* gtm_gt; const float* gtm_mom; int gtm_c, gtm_h, gtm_w;
-    // depth prior registered by the caller (st3r_ctx_set_depth_prior, loss_depth.hip): caller-owned, valid until cleared;
-    // dp_norm_valid: SLOT_DPRIOR_NORM holds the n_c of this registration (computed by the first training call that uses it)
-    const float* dp_gt; const float* dp_depth; const float* dp_weight; int dp_c, dp_h, dp_w; float dp_fac; int dp_norm_valid;
-    // exposures registered by the caller (st3r_ctx_set_exposure, gs_exposure.hip): caller-owned, valid until cleared
-    const float* ex_gt; const float* ex_exposure; float* ex_v_exposure; int ex_c, ex_h, ex_w;
+    // What the caller registered for a set of views (ViewReg) and each option's payload: caller-owned, valid until cleared.
+    // ground-truth moments (st3r_ctx_set_gt_moments, loss.hip)
+    ViewReg gtm; const float* gtm_mom;
+    // depth prior (st3r_ctx_set_depth_prior, loss_depth.hip); dp_fac == 0: none; dp_norm_valid: SLOT_DPRIOR_NORM holds
+    // the n_c of this registration (computed by the first training call that uses it)
+    ViewReg dp; const float* dp_depth; const float* dp_weight; float dp_fac; int dp_norm_valid;
+    // exposures (st3r_ctx_set_exposure, gs_exposure.hip)
+    ViewReg ex; const float* ex_exposure; float* ex_v_exposure;
     int bwd_stamp;  // generation stamp of the per-(record, tile) partial-gradient slots
     int depth_stamp;  // the same for the depth backward's slots (SLOT_VTILE_DEPTH)
     uint32_t scan_gen;   // single-pass scan (gs_isect.hip): generation of its status words

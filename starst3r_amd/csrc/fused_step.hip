@@ -391,7 +391,7 @@ static int train_views(st3r_ctx* ctx, hipStream_t s, const GsParams& g, const Vi
     rc = project_backward(ctx, s, g, v, ro, f, need_pairs ? v_pairs : nullptr, need_pairs ? nullptr : &slots, accumulate,
                           grads);
     // depth prior, inside the timing bracket: the pose gradient of the summed per-pair gradients first, then the float-9
-    // column into the means block and into row 2 of v_viewmats -- the order of _RasterizeDepth.backward
+    // column into the means block and into row 2 of v_viewmats -- the order of _Rasterize.backward
     if (!rc && need_pairs && b.v_viewmats) rc = pose_backward(ctx, s, g, v, ro, v_pairs, b.v_viewmats);
     if (!rc && need_pairs) rc = st3r_gs_depth_bwd(ctx, s, g.N, v.C, g.means, v.viewmats, ro.splats, v_pairs, grads, b.v_viewmats);
     st3r_prof_end(ctx, s, STG_PROJECT_BWD);

@@ -31,7 +31,7 @@
 #include "stages.h"
 #include "tile_rect.h"
 #include "blend_common.h"
-#include "project_common.h"
+#include "per_view.h"   // block_sum_fixed
 
 // q-form of record `id` in LDS slot t, two words: (x y opacity qa | qb qc z -) with qa, qb, qc formed exactly as
 // stage_qform forms them; returns the 4-bit quadrant relevance

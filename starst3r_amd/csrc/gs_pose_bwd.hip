@@ -17,7 +17,7 @@
 // each block sums its 256 pairs' 15 terms in double in a fixed order (wave butterfly, then the four waves in order) and
 // writes one partial; one workgroup per camera then sums that camera's partials in a fixed order and applies the
 // finisher.  Translation terms of a photometric loss cancel heavily over up to 10^6 pairs -- hence double.
-#include "common.h"
+#include "per_view.h"   // block_sum_fixed
 #include "project_common.h"
 
 #define POSE_VALS 15   // v_R (9, row-major), v_t (3), v_campos (3)

@@ -12,23 +12,17 @@
 //
 // The work is ~300 double operations per camera: one thread per camera, one launch, nothing to reduce.  What matters
 // is that it runs on the stream with no synchronisation, behind the same device-side guard as k_adam: a step that
-// outgrew its buffers moves no camera either.
+// outgrew its buffers moves no camera either.  Guard, mask, moment update and launch are the per-view Adam of
+// per_view.h, which k_exposure_adam shares; the tangent gradient and the retraction are this kernel's.
 // Non-finite gradients are NOT filtered (torch's Adam does not filter them either): a NaN or Inf in G goes through the
 // moments into V and campos of that camera, and stays.  The loss of such a step is non-finite too and says so.
-#include "stages.h"
+#include "per_view.h"
 
-struct PoseAdamK {
-    double lr, b1, b2, eps, bc1, bc2;
-};
-
-__global__ __launch_bounds__(64) void k_pose_adam(int C, float* __restrict__ viewmats, float* __restrict__ campos,
-                                                  const float* __restrict__ v_viewmats, float* __restrict__ pose_m,
-                                                  float* __restrict__ pose_v, PoseAdamK k, const float* __restrict__ mask,
-                                                  const int32_t* __restrict__ count_dev, uint32_t count_cap) {
-    if (count_dev && (uint32_t)count_dev[0] > count_cap) return;   // (see k_adam)
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= C) return;
-    if (mask && mask[c] == 0.0f) return;   // a frozen camera keeps V, campos, m and v bit for bit
+__global__ __launch_bounds__(64) void k_pose_adam(int C, PerViewAdamK k, float* __restrict__ viewmats,
+                                                  float* __restrict__ campos, const float* __restrict__ v_viewmats,
+                                                  float* __restrict__ pose_m, float* __restrict__ pose_v) {
+    const int c = per_view_adam_view(k, C);
+    if (c < 0) return;   // (a frozen camera keeps V, campos, m and v bit for bit)
     float* V = viewmats + 16 * c;
     const float* Gf = v_viewmats + 16 * c;
     double R[9], t[3], GR[9], Gt[3];
@@ -53,12 +47,7 @@ __global__ __launch_bounds__(64) void k_pose_adam(int C, float* __restrict__ vie
     // ---- Adam
     double d[6];
 #pragma unroll
-    for (int q = 0; q < 6; ++q) {
-        const double mi = k.b1 * (double)pose_m[6 * c + q] + (1.0 - k.b1) * g[q];
-        const double vi = k.b2 * (double)pose_v[6 * c + q] + ((1.0 - k.b2) * g[q]) * g[q];
-        pose_m[6 * c + q] = (float)mi; pose_v[6 * c + q] = (float)vi;
-        d[q] = -k.lr * (mi / k.bc1) / (sqrt(vi / k.bc2) + k.eps);
-    }
+    for (int q = 0; q < 6; ++q) d[q] = per_view_adam_delta<true>(k, pose_m[6 * c + q], g[q], pose_v[6 * c + q]);
     // ---- retraction: E = I + a K + b K^2,  K = [delta_omega]x,  K^2 = w w^T - |w|^2 I
     const double th2 = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2];
     double a, b;
@@ -99,28 +88,13 @@ __global__ __launch_bounds__(64) void k_pose_adam(int C, float* __restrict__ vie
     V[12] = 0.0f; V[13] = 0.0f; V[14] = 0.0f; V[15] = 1.0f;
 }
 
-static int pose_adam_launch(st3r_ctx* ctx, hipStream_t s, int C, float* viewmats, float* campos, const float* v_viewmats,
-                            float* pose_m, float* pose_v, double lr, double b1, double b2, double eps, int step,
-                            const float* mask) {
-    PoseAdamK k;
-    k.lr = lr; k.b1 = b1; k.b2 = b2; k.eps = eps;
-    k.bc1 = 1.0 - pow(b1, (double)step); k.bc2 = 1.0 - pow(b2, (double)step);
-    // an asynchronous step is in flight and its count not yet settled: guard the update with it (see k_adam)
-    const int32_t* count_dev; uint32_t count_cap;
-    st3r_adam_guard(ctx, &count_dev, &count_cap);
-    hipLaunchKernelGGL(k_pose_adam, dim3(ceil_div(C, 64)), dim3(64), 0, s, C, viewmats, campos, v_viewmats, pose_m, pose_v,
-                       k, mask, count_dev, count_cap);
-    LAUNCH_CHECK();
-    return ST3R_OK;
-}
-
 ST3R_EXPORT int st3r_pose_adam_step(st3r_ctx* ctx, void* stream, int C, float* viewmats, float* campos,
                                     const float* v_viewmats, float* pose_m, float* pose_v, double lr, double beta1,
                                     double beta2, double eps, int step, const float* mask) {
     ARG_CHECK(ctx && C > 0 && step >= 1 && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0);
     ARG_CHECK(viewmats && campos && v_viewmats && pose_m && pose_v);
-    return pose_adam_launch(ctx, (hipStream_t)stream, C, viewmats, campos, v_viewmats, pose_m, pose_v, lr, beta1, beta2,
-                            eps, step, mask);
+    return per_view_adam_launch(ctx, (hipStream_t)stream, k_pose_adam, C, lr, beta1, beta2, eps, step, mask, viewmats,
+                                campos, v_viewmats, pose_m, pose_v);
 }
 
 // st3r_gs_train_step that also moves the cameras.  Order: forward, loss, blend backward; Gaussian gradients AND the
@@ -154,6 +128,6 @@ ST3R_EXPORT int st3r_gs_train_step_poses(st3r_ctx* ctx, void* stream, int N, int
     rc = st3r_adam_step(ctx, stream, N, means, quats, scales, opacities, sh, sh_stride, grads, m, v, lr, beta1, beta2, eps,
                         step);
     if (rc) return rc;
-    return pose_adam_launch(ctx, (hipStream_t)stream, C, viewmats, campos, v_viewmats, pose_m, pose_v, pose_lr, beta1, beta2,
-                            eps, pose_step, pose_mask);
+    return per_view_adam_launch(ctx, (hipStream_t)stream, k_pose_adam, C, pose_lr, beta1, beta2, eps, pose_step, pose_mask,
+                                viewmats, campos, v_viewmats, pose_m, pose_v);
 }

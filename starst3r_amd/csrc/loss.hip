@@ -520,12 +520,8 @@ __global__ __launch_bounds__(FT2) __attribute__((amdgpu_waves_per_eu(GTM ? SSIM_
 
 // the registered ground-truth moments that belong to the images at `gt` (NULL: none -- the kernel convolves y itself)
 static const float2* gt_moments_for(const st3r_ctx* ctx, const float* gt, int C, int H, int W) {
-    if (!ctx->gtm_mom || H != ctx->gtm_h || W != ctx->gtm_w) return nullptr;
-    const int64_t img = (int64_t)H * W * 3;
-    if (gt < ctx->gtm_gt || (gt - ctx->gtm_gt) % img != 0) return nullptr;
-    const int64_t c0 = (gt - ctx->gtm_gt) / img;
-    if (c0 + C > ctx->gtm_c) return nullptr;
-    return reinterpret_cast<const float2*>(ctx->gtm_mom) + c0 * img;
+    const int64_t c0 = view_reg_first(ctx->gtm, gt, C, H, W);
+    return c0 < 0 ? nullptr : reinterpret_cast<const float2*>(ctx->gtm_mom) + c0 * H * W * 3;
 }
 
 int st3r_loss_impl(st3r_ctx* ctx, hipStream_t s, int C, int H, int W, const float* render, const float* gt,
@@ -584,10 +580,10 @@ ST3R_EXPORT int st3r_loss_gt_moments(st3r_ctx* ctx, void* stream, int C, int hei
 ST3R_EXPORT int st3r_ctx_set_gt_moments(st3r_ctx* ctx, const float* gt, const float* moments, int C, int height,
                                         int width) {
     ARG_CHECK(ctx);
-    if (!gt || !moments) { ctx->gtm_gt = nullptr; ctx->gtm_mom = nullptr; ctx->gtm_c = ctx->gtm_h = ctx->gtm_w = 0; return ST3R_OK; }
-    ARG_CHECK(C > 0 && height > 0 && width > 0);
-    ctx->gtm_gt = gt; ctx->gtm_mom = moments; ctx->gtm_c = C; ctx->gtm_h = height; ctx->gtm_w = width;
-    return ST3R_OK;
+    const bool on = gt && moments;
+    int rc = view_reg_set(&ctx->gtm, on, gt, C, height, width);
+    if (!rc) ctx->gtm_mom = on ? moments : nullptr;
+    return rc;
 }
 
 ST3R_EXPORT int st3r_loss_l1_ssim(st3r_ctx* ctx, void* stream, int C, int height, int width, const float* render,

@@ -1,6 +1,6 @@
 // What gs_project.hip, gs_project_bwd.hip and gs_pose_bwd.hip share: the SH constants, the layout of the per-camera
-// block, the conic part of the pair chain rule, and the fixed-order block sum of doubles that gs_pose_bwd.hip has in
-// common with gs_blend_depth.hip.
+// block and the conic part of the pair chain rule.  (The fixed-order block sum of doubles that gs_pose_bwd.hip has in
+// common with gs_blend_depth.hip is per_view.h's.)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -41,25 +41,4 @@ __device__ __forceinline__ void conic_chain(const float4& r0, const float4& r1, 
     vJ02 = 2.0f * (GJ00 * S.xz + GJ01 * S.yz + GJ02 * S.zz);
     vJ11 = 2.0f * (GJ10 * S.xy + GJ11 * S.yy + GJ12 * S.yz);
     vJ12 = 2.0f * (GJ10 * S.xz + GJ11 * S.yz + GJ12 * S.zz);
-}
-
-// Sum of v[k] over the 256 threads of a workgroup in a fixed order (wave butterfly, then the four waves in order):
-// thread k < NV returns the sum of v[k], the other threads 0.  red: 4 * NV doubles of LDS that no thread still reads
-// (a loop around the call needs a barrier between one call's reads and the next call's writes).
-template <int NV>
-__device__ __forceinline__ double block_sum_fixed(double (&v)[NV], double* red) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_xor(v[k], off, 64);
-    }
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < NV; ++k) red[wv * NV + k] = v[k];
-    }
-    __syncthreads();
-    if (threadIdx.x >= NV) return 0.0;
-    const int k = threadIdx.x;
-    return ((red[k] + red[NV + k]) + red[2 * NV + k]) + red[3 * NV + k];
 }

@@ -105,9 +105,7 @@ int st3r_add_pairs_impl(hipStream_t s, int64_t n_pairs, float* a, const float* b
 // ---- loss.hip, loss_depth.hip ----
 int st3r_loss_impl(st3r_ctx* ctx, hipStream_t s, int C, int H, int W, const float* render, const float* gt,
                    float w_l1, float w_ssim, double* sums, float* v_render, bool sums_cleared);
-// how the streaming per-view kernels (k_dprior_loss, k_exposure_fwd / _bwd) deal HW pixels of C views to workgroups of 256
-// threads: contiguous chunks of a multiple of 1024 pixels, at most 2048 workgroups in all
-void st3r_stream_grid(int C, int64_t HW, int* blocks, int64_t* chunk);
+// (st3r_stream_grid, which gs_exposure.hip calls too, is declared with the streaming scaffold in per_view.h)
 int st3r_depth_prior_for(st3r_ctx* ctx, hipStream_t s, const float* gt, int C, int H, int W, DepthPrior* out);
 int st3r_depth_prior_loss_impl(st3r_ctx* ctx, hipStream_t s, int C, int H, int W, const float* depth, const float* alpha,
                                const float* prior, const float* weight, const double* norm, int norm_stride,

@@ -189,66 +189,36 @@ def init_3dgs(scene, init_scale=3e-3, lr=1e-3):
     scene._gt_dev = None
 
 
-class _Rasterize(torch.autograd.Function):
-    """Differentiable wrapper so user code can still back-propagate through render_3dgs: into the Gaussians and, when
-    w2c requires a gradient, into the camera poses."""
-
-    @staticmethod
-    def forward(fctx, means, quats, scales, opacities, shN, w2c, Ks, width, height, ctx):
-        rgb, alpha, info = ops.rasterization(ctx, means, quats, scales, opacities, shN, w2c, Ks, width, height)
-        fctx.save_for_backward(means, quats, scales, opacities, shN, w2c, Ks, alpha)
-        fctx.info, fctx.ctx, fctx.wh = info, ctx, (width, height)
-        return rgb, alpha
-
-    @staticmethod
-    def backward(fctx, v_rgb, v_alpha):
-        means, quats, scales, opacities, shN, w2c, Ks, alpha = fctx.saved_tensors
-        info, ctx, (W, H) = fctx.info, fctx.ctx, fctx.wh
-        Cn = w2c.shape[0]
-        # the backward consumes the contribution masks the forward left in the ctx: re-run the blend forward so
-        # that they belong to THIS rasterization even if other renders happened in between
-        ops.blend_fwd(ctx, info["_splats"], info["isect_offsets"], info["_flatten_ids_dense"], Cn, W, H)
-        v_splats = ops.blend_bwd(ctx, info["_splats"], info["isect_offsets"], info["_flatten_ids_dense"], alpha,
-                                 info["_last_ids"], v_rgb.contiguous().float(),
-                                 None if v_alpha is None else v_alpha.contiguous().float(), info["_cum_tiles"], Cn, W, H)
-        grads = ops.project_sh_bwd(ctx, means, quats, scales, opacities, shN, w2c, Ks, info["_campos"], W, H,
-                                   info["_splats"], v_splats)
-        G = ops.split_grads(grads, means.shape[0])
-        v_sh = torch.zeros_like(shN)
-        v_sh[:, :4] = G["sh"]
-        # camera poses: only when asked for (gsplat's v_viewmats); intrinsics get none, as in gsplat
-        v_w2c = None
-        if fctx.needs_input_grad[5]:
-            v_w2c = ops.viewmat_bwd(ctx, means, quats, scales, shN, w2c, Ks, info["_campos"], W, H, info["_splats"],
-                                    v_splats)
-        return G["means"], G["quats"], G["scales"], G["opacities"], v_sh, v_w2c, None, None, None, None
-
-
 RENDER_MODES = ("RGB", "D", "ED", "RGB+D", "RGB+ED")   # gsplat.rasterization's render_mode
 
 
-class _RasterizeDepth(torch.autograd.Function):
-    """_Rasterize plus the depth map of the same render (st3r_gs_blend_depth_fwd): returns (rgb, alpha, depth) and
-    back-propagates from any of them.  The per-pair gradients of the colour and of the depth backward are summed and go
+class _Rasterize(torch.autograd.Function):
+    """Differentiable wrapper so user code can still back-propagate through render_3dgs: into the Gaussians and, when
+    w2c requires a gradient, into the camera poses.  want_depth: returns (rgb, alpha, depth) -- the depth map of the same
+    render (st3r_gs_blend_depth_fwd) -- and back-propagates from any of them; without it (rgb, alpha), and no depth
+    kernel runs, forward or backward.  The per-pair gradients of the colour and of the depth backward are summed and go
     through project_sh_bwd / viewmat_bwd once; the depth column (z of the record) is added by st3r_gs_depth_bwd."""
 
     @staticmethod
-    def forward(fctx, means, quats, scales, opacities, shN, w2c, Ks, width, height, ctx):
+    def forward(fctx, means, quats, scales, opacities, shN, w2c, Ks, width, height, ctx, want_depth):
         rgb, alpha, info = ops.rasterization(ctx, means, quats, scales, opacities, shN, w2c, Ks, width, height)
-        depth = ops.blend_depth_fwd(ctx, info["_splats"], info["isect_offsets"], info["_flatten_ids_dense"], alpha,
-                                    info["_last_ids"], w2c.shape[0], width, height)
         fctx.save_for_backward(means, quats, scales, opacities, shN, w2c, Ks, alpha)
         fctx.info, fctx.ctx, fctx.wh = info, ctx, (width, height)
+        if not want_depth:
+            return rgb, alpha
         fctx.set_materialize_grads(False)   # an output the loss does not use costs no backward kernel
+        depth = ops.blend_depth_fwd(ctx, info["_splats"], info["isect_offsets"], info["_flatten_ids_dense"], alpha,
+                                    info["_last_ids"], w2c.shape[0], width, height)
         return rgb, alpha, depth
 
     @staticmethod
-    def backward(fctx, v_rgb, v_alpha, v_depth):
+    def backward(fctx, v_rgb, v_alpha, v_depth=None):
         means, quats, scales, opacities, shN, w2c, Ks, alpha = fctx.saved_tensors
         info, ctx, (W, H) = fctx.info, fctx.ctx, fctx.wh
         Cn, N = w2c.shape[0], means.shape[0]
         lists = (info["_splats"], info["isect_offsets"], info["_flatten_ids_dense"])
-        # both backward kernels consume the contribution masks of THIS rasterization (see _Rasterize.backward)
+        # the backward kernels consume the contribution masks the forward left in the ctx: re-run the blend forward so
+        # that they belong to THIS rasterization even if other renders happened in between
         ops.blend_fwd(ctx, *lists, Cn, W, H)
         v_splats = None
         if v_rgb is not None or v_alpha is not None:
@@ -263,6 +233,7 @@ class _RasterizeDepth(torch.autograd.Function):
             v_splats = torch.zeros_like(info["_splats"])
         grads = ops.project_sh_bwd(ctx, means, quats, scales, opacities, shN, w2c, Ks, info["_campos"], W, H,
                                    info["_splats"], v_splats)
+        # camera poses: only when asked for (gsplat's v_viewmats); intrinsics get none, as in gsplat
         v_w2c = None
         if fctx.needs_input_grad[5]:
             v_w2c = ops.viewmat_bwd(ctx, means, quats, scales, shN, w2c, Ks, info["_campos"], W, H, info["_splats"],
@@ -272,7 +243,7 @@ class _RasterizeDepth(torch.autograd.Function):
         G = ops.split_grads(grads, N)
         v_sh = torch.zeros_like(shN)
         v_sh[:, :4] = G["sh"]
-        return G["means"], G["quats"], G["scales"], G["opacities"], v_sh, v_w2c, None, None, None, None
+        return G["means"], G["quats"], G["scales"], G["opacities"], v_sh, v_w2c, None, None, None, None, None
 
 
 class _Exposure(torch.autograd.Function):
@@ -320,13 +291,13 @@ def render_3dgs(scene, w2c: torch.Tensor, intrinsics: torch.Tensor, width: int, 
     w2c = w2c.to(scene.device, torch.float32).contiguous(); Ks = intrinsics.to(scene.device, torch.float32).contiguous()
     if exposure is not None:
         exposure = exposure.to(scene.device, torch.float32)
+    out = _Rasterize.apply(g["means"], g["quats"], g["scales"], g["opacities"], g["shN"], w2c, Ks, width, height, ctx,
+                           render_mode != "RGB")
     if render_mode == "RGB":
-        rgb, alpha = _Rasterize.apply(g["means"], g["quats"], g["scales"], g["opacities"], g["shN"], w2c, Ks, width,
-                                      height, ctx)
+        rgb, alpha = out
         img = rgb if exposure is None else _Exposure.apply(rgb, exposure, ctx)
     else:
-        rgb, alpha, depth = _RasterizeDepth.apply(g["means"], g["quats"], g["scales"], g["opacities"], g["shN"], w2c, Ks,
-                                                  width, height, ctx)
+        rgb, alpha, depth = out
         if render_mode.endswith("ED"):
             depth = depth / alpha.clamp(min=1e-10)
         if exposure is not None and render_mode.startswith("RGB"):
@@ -407,6 +378,40 @@ def _exposure_frozen(n_views, exposure_freeze):
     return sorted(out)
 
 
+def _on(value, schedule=False):
+    """is the option this rate or factor belongs to switched on: not 0.0 or, for a rate, a callable schedule"""
+    return (schedule and callable(value)) or float(value) != 0.0
+
+
+def _rate_at(rate, step):
+    """value at `step` of a rate given as a float or as a callable step -> float"""
+    return float(rate(step)) if callable(rate) else float(rate)
+
+
+def _freeze_mask(n, frozen, device):
+    """[n] ones, zeros at the sorted indices `frozen`: the mask of the per-view Adam steps"""
+    mask = torch.ones(n, device=device)
+    if frozen:
+        mask[frozen] = 0.0
+    return mask
+
+
+def _per_view_moments(st, name, n, device):
+    """st.<name>_m, st.<name>_v ([n] zeros) and st.<name>_step (0): made on first use or when n changed, else kept"""
+    m = getattr(st, name + "_m", None)
+    if m is None or m.numel() != n:
+        setattr(st, name + "_m", torch.zeros(n, device=device))
+        setattr(st, name + "_v", torch.zeros(n, device=device))
+        setattr(st, name + "_step", 0)
+
+
+def _single_replica_only(option, scene, enable_pruning):
+    """the refusal of a per-view option (named as the user spelled it) under torch.distributed or the sharded layout"""
+    if _dist.rank_world()[1] > 1 or _sharded_layout(scene, 1, enable_pruning):
+        raise NotImplementedError(f"{option} != 0 is supported in a single process with replicated Gaussians only "
+                                  "(not under torch.distributed, not with ST3R_MULTI_GPU=gaussian-sharded)")
+
+
 def run_3dgs_optim(
         scene,
         iters: int,
@@ -454,19 +459,14 @@ def run_3dgs_optim(
     pose_lr, depth_fac and enable_pruning; single process, Gaussians replicated only.  With exposure_lr == 0 nothing about
     the call changes and scene.exposures is not created.
     """
-    poses_on = callable(pose_lr) or float(pose_lr) != 0.0
-    depth_on = float(depth_fac) != 0.0
-    if depth_on and (_dist.rank_world()[1] > 1 or _sharded_layout(scene, 1, enable_pruning)):
-        raise NotImplementedError("depth_fac != 0 is supported in a single process with replicated Gaussians only "
-                                  "(not under torch.distributed, not with ST3R_MULTI_GPU=gaussian-sharded)")
-    if poses_on and (_dist.rank_world()[1] > 1 or _sharded_layout(scene, 1, enable_pruning)):
-        raise NotImplementedError("pose_lr != 0 is supported in a single process with replicated Gaussians only "
-                                  "(not under torch.distributed, not with ST3R_MULTI_GPU=gaussian-sharded)")
-    exposure_on = callable(exposure_lr) or float(exposure_lr) != 0.0
-    if exposure_on and (_dist.rank_world()[1] > 1 or _sharded_layout(scene, 1, enable_pruning)):
-        raise NotImplementedError("exposure_lr != 0 is supported in a single process with replicated Gaussians only "
-                                  "(not under torch.distributed, not with ST3R_MULTI_GPU=gaussian-sharded)")
+    poses_on, depth_on = _on(pose_lr, schedule=True), _on(depth_fac)
+    if depth_on:
+        _single_replica_only("depth_fac", scene, enable_pruning)
+    if poses_on:
+        _single_replica_only("pose_lr", scene, enable_pruning)
+    exposure_on = _on(exposure_lr, schedule=True)
     if exposure_on:   # (checked before anything runs)
+        _single_replica_only("exposure_lr", scene, enable_pruning)
         exp_frozen = _exposure_frozen(len(scene.imgs), exposure_freeze)
     height, width = scene.imgs[0].shape[:2]
     ctx = ops.get_context(scene.device)
@@ -490,13 +490,9 @@ def run_3dgs_optim(
         # a private copy: the tensor Scene.w2c caches is never trained (w2c_all may BE that tensor)
         w2c = w2c.clone()
         n_cam = w2c.shape[0]
-        if getattr(st, "pose_m", None) is None or st.pose_m.numel() != 6 * n_cam:   # first use, or the views changed
-            st.pose_m = torch.zeros(6 * n_cam, device=w2c.device); st.pose_v = torch.zeros_like(st.pose_m)
-            st.pose_step = 0
+        _per_view_moments(st, "pose", 6 * n_cam, w2c.device)   # (new when the views changed)
         frozen = sorted({int(i) % n_cam for i in pose_freeze})
-        pose_mask = torch.ones(n_cam, device=w2c.device)
-        if frozen:
-            pose_mask[frozen] = 0.0
+        pose_mask = _freeze_mask(n_cam, frozen, w2c.device)
         st.pose_w2c = w2c   # the matrices being trained (diagnostics; scene.c2w follows when the loop ends)
     if exposure_on:
         n_img = len(scene.imgs)
@@ -506,13 +502,9 @@ def run_3dgs_optim(
         if E.dtype != torch.float32 or E.device != gt.device or not E.is_contiguous():
             E = E.detach().to(gt.device, torch.float32).contiguous()
         scene.exposures = E   # trained in place
-        if getattr(st, "exp_m", None) is None or st.exp_m.numel() != 12 * n_img:
-            st.exp_m = torch.zeros(12 * n_img, device=gt.device); st.exp_v = torch.zeros_like(st.exp_m)
-            st.exp_step = 0
+        _per_view_moments(st, "exp", 12 * n_img, gt.device)
         st.exp_grad = torch.zeros((n_img, 3, 4), device=gt.device)   # this step's d loss / d exposures (diagnostics)
-        exp_mask = torch.ones(n_img, device=gt.device)
-        if exp_frozen:
-            exp_mask[exp_frozen] = 0.0
+        exp_mask = _freeze_mask(n_img, exp_frozen, gt.device)
     restore_exchange = None
     if enable_pruning and fused and world > 1 and ops.get_exchange(ctx) in ("rs_ag", "direct"):
         # reduce-scatter exchange (through RCCL or through the peers' exported buffers): a rank maintains the Adam moments of its piece of the buffer only; growing the set
@@ -543,8 +535,7 @@ def run_3dgs_optim(
             ops.train_step_poses(ctx, P, w2c, Ks, campos, gt, width, height, loss_ssim_fac, loss_opacity_fac,
                                  loss_scale_fac, st.grads, st.m, st.v, st.lr, st.betas[0], st.betas[1], st.eps, st.step,
                                  losses[step:step + 1], st.pose_m, st.pose_v,
-                                 float(pose_lr(step)) if callable(pose_lr) else float(pose_lr), st.pose_step, pose_mask,
-                                 want_stats=False)
+                                 _rate_at(pose_lr, step), st.pose_step, pose_mask, want_stats=False)
         elif fused:   # the whole iteration is one C call (gradient all-reduce inside, over the ctx's communicator)
             # no host round trip in steady state (single rank; with a communicator the library sizes every step exactly)
             ops.train_step(ctx, P, w2c, Ks, campos, gt, width, height, loss_ssim_fac, loss_opacity_fac,
@@ -557,9 +548,8 @@ def run_3dgs_optim(
             _dist.all_reduce_sum(st.grads)
             ops.adam_step(ctx, P, st.grads, st.m, st.v, st.lr, st.betas[0], st.betas[1], st.eps, st.step)
         if exposure_on:   # behind the step on the same stream, and behind the same device-side guard as its updates
-            ops.exposure_adam_step(ctx, scene.exposures, st.exp_grad, st.exp_m, st.exp_v,
-                                   float(exposure_lr(step)) if callable(exposure_lr) else float(exposure_lr), st.betas[0],
-                                   st.betas[1], st.eps, st.exp_step, exp_mask)
+            ops.exposure_adam_step(ctx, scene.exposures, st.exp_grad, st.exp_m, st.exp_v, _rate_at(exposure_lr, step),
+                                   st.betas[0], st.betas[1], st.eps, st.exp_step, exp_mask)
 
     def capacity_error(e):
         return getattr(e, "code", 0) == -3 and world == 1
@@ -576,9 +566,9 @@ def run_3dgs_optim(
     # our own strategy reads the parameters in step_post_backward only, and the SH rows on refinement steps only
     # (relocation / growth copy whole rows); any OTHER strategy object sees up-to-date rows at every hook call
     own_strategy = type(scene.strategy) is MCMCStrategy
-    ops.set_gt_moments(ctx, gt, _gt_moments(scene, ctx, gt))
-    try:
-        if depth_on:   # the prior belongs to this call: cleared below whatever ends the loop
+    try:   # what is registered belongs to this call: cleared below whatever ends the loop, a failing registration included
+        ops.set_gt_moments(ctx, gt, _gt_moments(scene, ctx, gt))
+        if depth_on:
             ops.set_depth_prior(ctx, gt, prior, prior_w, float(depth_fac))
         if exposure_on:   # and so do the exposures
             ops.set_exposure(ctx, gt, scene.exposures, st.exp_grad)
@@ -727,8 +717,8 @@ def _run_3dgs_optim_sharded(scene, iters, ssim_fac, opac_fac, scale_fac, verbose
         from tqdm import trange
         it_range = trange(iters)
     strategy, state = scene.strategy, scene.strategy_state
-    ops.set_gt_moments(ctx, gt, _gt_moments(scene, ctx, gt))
     try:
+        ops.set_gt_moments(ctx, gt, _gt_moments(scene, ctx, gt))
         for step in it_range:
             tr.step(losses[step:step + 1])
             if enable_pruning:   # MCMCStrategy.step_post_backward, shard-wise

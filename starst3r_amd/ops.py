@@ -103,6 +103,33 @@ def sh_stride_of(sh):
     return int(sh.numel() // sh.shape[0])
 
 
+def _gaussians(params):
+    """the argument run `means, quats, scales, opacities, sh, sh_stride` of the C calls, from a params dict"""
+    sh = params["shN"]
+    return (_p(params["means"]), _p(params["quats"]), _p(params["scales"]), _p(params["opacities"]), _p(sh),
+            sh_stride_of(sh))
+
+
+def _stats(stats):
+    """the statistics a training call wrote (int64[4]) as a dict; None when none were asked for"""
+    if stats is None:
+        return None
+    return dict(n_visible=int(stats[0]), n_isects=int(stats[1]), arena_bytes=int(stats[2]), n_isects_ref=int(stats[3]))
+
+
+def _set_registration(ctx, name, keep, gt, payload, shapes_ok, *extra):
+    """The body of set_gt_moments, set_depth_prior and set_exposure: st3r_ctx_set_<name> on (gt, *payload, C, H, W,
+    *extra), or with a None among the tensors the call that clears it.  The attribute `keep` of ctx keeps the tensors alive."""
+    fn = getattr(_lib.lib(), "st3r_ctx_set_" + name)
+    if gt is None or any(t is None for t in payload):
+        _lib.check(fn(ctx.handle, None, *(None for _ in payload), 0, 0, 0, *(0.0 for _ in extra)))
+        setattr(ctx, keep, None)
+        return
+    assert gt.is_contiguous() and shapes_ok()
+    _lib.check(fn(ctx.handle, _p(gt), *(_p(t) for t in payload), gt.shape[0], gt.shape[1], gt.shape[2], *extra))
+    setattr(ctx, keep, (gt, *payload))
+
+
 def project_sh(ctx, means, quats, scales, opacities, sh, viewmats, Ks, campos, W, H, reg_sums=None,
                eps2d=0.3, near=0.01, far=1e10, radius_clip=0.0, out=None):
     """out: optional (splats [Cn*N,12], tiles int32 [Cn*N]) buffers to write into (steady-state loops)."""
@@ -273,13 +300,8 @@ def gt_moments(ctx, gt):
 def set_gt_moments(ctx, gt, moments):
     """Register (gt, moments) with the ctx -- the loss kernels then read the moments instead of convolving gt -- or clear
     the registration (gt = None).  The caller keeps both tensors alive and unchanged while registered."""
-    if gt is None or moments is None:
-        _lib.check(_lib.lib().st3r_ctx_set_gt_moments(ctx.handle, None, None, 0, 0, 0))
-        ctx._gtm_keep = None
-        return
-    assert gt.is_contiguous() and moments.is_contiguous() and moments.shape == (*gt.shape, 2)
-    _lib.check(_lib.lib().st3r_ctx_set_gt_moments(ctx.handle, _p(gt), _p(moments), gt.shape[0], gt.shape[1], gt.shape[2]))
-    ctx._gtm_keep = (gt, moments)
+    _set_registration(ctx, "gt_moments", "_gtm_keep", gt, (moments,),
+                      lambda: moments.is_contiguous() and moments.shape == (*gt.shape, 2))
 
 
 def loss_depth_prior(ctx, depth, alpha, prior, weight, depth_fac):
@@ -300,14 +322,8 @@ def set_depth_prior(ctx, gt, depth, weight, depth_fac=1.0):
     and train_step_poses on `gt` (or whole views of it) then add depth_fac * sum_p w |ED - Z| / max(sum_p w, 1) per view to
     their loss (st3r_ctx_set_depth_prior) -- or clear the registration (gt = None).  The caller's tensors are kept alive
     here and must stay unchanged while registered."""
-    if gt is None or depth is None or weight is None:
-        _lib.check(_lib.lib().st3r_ctx_set_depth_prior(ctx.handle, None, None, None, 0, 0, 0, 0.0))
-        ctx._dp_keep = None
-        return
-    assert gt.is_contiguous() and depth.shape == tuple(gt.shape[:3]) and weight.shape == tuple(gt.shape[:3])
-    _lib.check(_lib.lib().st3r_ctx_set_depth_prior(ctx.handle, _p(gt), _p(depth), _p(weight), gt.shape[0], gt.shape[1],
-                                                   gt.shape[2], float(depth_fac)))
-    ctx._dp_keep = (gt, depth, weight)
+    _set_registration(ctx, "depth_prior", "_dp_keep", gt, (depth, weight),
+                      lambda: depth.shape == tuple(gt.shape[:3]) and weight.shape == tuple(gt.shape[:3]), float(depth_fac))
 
 
 def _exposure_shapes(rgb, exposure):
@@ -352,58 +368,42 @@ def set_exposure(ctx, gt, exposure, v_exposure):
     gradient -- train_fwd_bwd, train_step and train_step_poses on `gt` (or whole views of it) then compare the exposed
     render with the ground truth and write v_exposure (st3r_ctx_set_exposure) -- or clear the registration (gt = None).
     The caller's tensors are kept alive here."""
-    if gt is None or exposure is None or v_exposure is None:
-        _lib.check(_lib.lib().st3r_ctx_set_exposure(ctx.handle, None, None, None, 0, 0, 0))
-        ctx._ex_keep = None
-        return
-    assert gt.is_contiguous() and tuple(exposure.shape) == (gt.shape[0], 3, 4) and v_exposure.shape == exposure.shape
-    _lib.check(_lib.lib().st3r_ctx_set_exposure(ctx.handle, _p(gt), _p(exposure), _p(v_exposure), gt.shape[0], gt.shape[1],
-                                                gt.shape[2]))
-    ctx._ex_keep = (gt, exposure, v_exposure)
+    _set_registration(ctx, "exposure", "_ex_keep", gt, (exposure, v_exposure),
+                      lambda: tuple(exposure.shape) == (gt.shape[0], 3, 4) and v_exposure.shape == exposure.shape)
 
 
 def adam_step(ctx, params, grads, m, v, lr, b1, b2, eps, step):
     """params: dict with means, quats, scales, opacities, shN (updated in place)."""
     N = params["means"].shape[0]
-    sh = params["shN"]
-    _lib.check(_lib.lib().st3r_adam_step(ctx.handle, _stream(), N, _p(params["means"]), _p(params["quats"]),
-                                         _p(params["scales"]), _p(params["opacities"]), _p(sh), sh_stride_of(sh),
-                                         _p(grads), _p(m), _p(v), lr, b1, b2, eps, step))
+    _lib.check(_lib.lib().st3r_adam_step(ctx.handle, _stream(), N, *_gaussians(params), _p(grads), _p(m), _p(v), lr, b1,
+                                         b2, eps, step))
 
 
 def train_fwd_bwd(ctx, params, viewmats, Ks, campos, gt, W, H, ssim_fac, opac_fac, scale_fac, grads, loss_out,
                   want_stats=True):
     """want_stats=False: see train_step."""
     N, Cn = params["means"].shape[0], viewmats.shape[0]
-    sh = params["shN"]
     stats = (C.c_int64 * 4)() if want_stats else None
     _lib.check(_lib.lib().st3r_gs_train_fwd_bwd(
-        ctx.handle, _stream(), N, Cn, _p(params["means"]), _p(params["quats"]), _p(params["scales"]),
-        _p(params["opacities"]), _p(sh), sh_stride_of(sh), _p(viewmats), _p(Ks), _p(campos), _p(gt), W, H, ssim_fac,
+        ctx.handle, _stream(), N, Cn, *_gaussians(params), _p(viewmats), _p(Ks), _p(campos), _p(gt), W, H, ssim_fac,
         opac_fac, scale_fac, _p(grads), _p(loss_out), stats))
-    if not want_stats:
-        return None
-    return dict(n_visible=int(stats[0]), n_isects=int(stats[1]), arena_bytes=int(stats[2]), n_isects_ref=int(stats[3]))
+    return _stats(stats)
 
 
 def adam_step_range(ctx, params, grads, m, v, lr, b1, b2, eps, step, i0, i1, stage=None):
     """Adam on the scalars [i0, i1) of the 23N-float buffers (the piece a rank owns after a reduce-scatter); `stage`
     (23N floats, buffer order) receives the new parameter values of the piece."""
     N = params["means"].shape[0]
-    sh = params["shN"]
     _lib.check(_lib.lib().st3r_adam_step_range(
-        ctx.handle, _stream(), N, _p(params["means"]), _p(params["quats"]), _p(params["scales"]), _p(params["opacities"]),
-        _p(sh), sh_stride_of(sh), _p(grads), _p(m), _p(v), lr, b1, b2, eps, step, int(i0), int(i1),
-        _p(stage) if stage is not None else None))
+        ctx.handle, _stream(), N, *_gaussians(params), _p(grads), _p(m), _p(v), lr, b1, b2, eps, step, int(i0), int(i1),
+        _p(stage)))
 
 
 def params_from_stage(ctx, params, stage, i0, i1, limit):
     """parameters of the scalars outside [i0, i1) and below `limit` <- stage (buffer order)."""
     N = params["means"].shape[0]
-    sh = params["shN"]
-    _lib.check(_lib.lib().st3r_params_from_stage(
-        ctx.handle, _stream(), N, _p(params["means"]), _p(params["quats"]), _p(params["scales"]), _p(params["opacities"]),
-        _p(sh), sh_stride_of(sh), _p(stage), int(i0), int(i1), int(limit)))
+    _lib.check(_lib.lib().st3r_params_from_stage(ctx.handle, _stream(), N, *_gaussians(params), _p(stage), int(i0),
+                                                 int(i1), int(limit)))
 
 
 def train_step(ctx, params, viewmats, Ks, campos, gt, W, H, ssim_fac, opac_fac, scale_fac, grads, m, v, lr, b1, b2, eps,
@@ -413,15 +413,11 @@ def train_step(ctx, params, viewmats, Ks, campos, gt, W, H, ssim_fac, opac_fac, 
     want_stats=False: no statistics come back and the call does not synchronise with the device in steady state (the
     record count stays on the device; see st3r_gs_train_fwd_bwd in include/st3r.h)."""
     N, Cn = params["means"].shape[0], viewmats.shape[0]
-    sh = params["shN"]
     stats = (C.c_int64 * 4)() if want_stats else None
     _lib.check(_lib.lib().st3r_gs_train_step(
-        ctx.handle, _stream(), N, Cn, _p(params["means"]), _p(params["quats"]), _p(params["scales"]),
-        _p(params["opacities"]), _p(sh), sh_stride_of(sh), _p(viewmats), _p(Ks), _p(campos), _p(gt), W, H, ssim_fac,
+        ctx.handle, _stream(), N, Cn, *_gaussians(params), _p(viewmats), _p(Ks), _p(campos), _p(gt), W, H, ssim_fac,
         opac_fac, scale_fac, _p(grads), _p(m), _p(v), lr, b1, b2, eps, step, _p(loss_out), stats))
-    if not want_stats:
-        return None
-    return dict(n_visible=int(stats[0]), n_isects=int(stats[1]), arena_bytes=int(stats[2]), n_isects_ref=int(stats[3]))
+    return _stats(stats)
 
 
 def pose_adam_step(ctx, viewmats, campos, v_viewmats, pose_m, pose_v, lr, b1, b2, eps, step, mask=None):
@@ -441,16 +437,12 @@ def train_step_poses(ctx, params, viewmats, Ks, campos, gt, W, H, ssim_fac, opac
     gradients belong to the poses the call started with.  pose_mask [C] floats: 0 freezes a camera.  v_viewmats_out
     [C,4,4]: receives this step's pose gradient.  want_stats as in train_step."""
     N, Cn = params["means"].shape[0], viewmats.shape[0]
-    sh = params["shN"]
     stats = (C.c_int64 * 4)() if want_stats else None
     _lib.check(_lib.lib().st3r_gs_train_step_poses(
-        ctx.handle, _stream(), N, Cn, _p(params["means"]), _p(params["quats"]), _p(params["scales"]),
-        _p(params["opacities"]), _p(sh), sh_stride_of(sh), _p(viewmats), _p(Ks), _p(campos), _p(gt), W, H, ssim_fac,
+        ctx.handle, _stream(), N, Cn, *_gaussians(params), _p(viewmats), _p(Ks), _p(campos), _p(gt), W, H, ssim_fac,
         opac_fac, scale_fac, _p(grads), _p(m), _p(v), lr, b1, b2, eps, step, _p(loss_out), stats, _p(pose_m), _p(pose_v),
         pose_lr, pose_step, _p(pose_mask), _p(v_viewmats_out)))
-    if not want_stats:
-        return None
-    return dict(n_visible=int(stats[0]), n_isects=int(stats[1]), arena_bytes=int(stats[2]), n_isects_ref=int(stats[3]))
+    return _stats(stats)
 
 
 def dense_unproject(ctx, view_start, pixels, idxs, offsets, core, cam_rows, base_focals):
@@ -615,15 +607,12 @@ def stage_ms(ctx):
 
 def render(ctx, params, viewmats, Ks, campos, W, H):
     N, Cn = params["means"].shape[0], viewmats.shape[0]
-    sh = params["shN"]
     dev = params["means"].device
     rgb = torch.empty((Cn, H, W, 3), dtype=torch.float32, device=dev)
     alpha = torch.empty((Cn, H, W, 1), dtype=torch.float32, device=dev)
     stats = (C.c_int64 * 4)()
-    _lib.check(_lib.lib().st3r_gs_render(
-        ctx.handle, _stream(), N, Cn, _p(params["means"]), _p(params["quats"]), _p(params["scales"]),
-        _p(params["opacities"]), _p(sh), sh_stride_of(sh), _p(viewmats), _p(Ks), _p(campos), W, H, _p(rgb), _p(alpha),
-        stats))
+    _lib.check(_lib.lib().st3r_gs_render(ctx.handle, _stream(), N, Cn, *_gaussians(params), _p(viewmats), _p(Ks),
+                                         _p(campos), W, H, _p(rgb), _p(alpha), stats))
     return rgb, alpha, dict(n_isects=int(stats[1]))
 
 

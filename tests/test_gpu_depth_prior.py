@@ -114,6 +114,32 @@ def test_loss_kernel_vs_fp64(ctx, shape):
     assert _same_bits(v_d, v_d2) and _same_bits(v_a, v_a2)
 
 
+def test_loss_kernel_on_unaligned_buffers(ctx):
+    """(3,16,64) has H * W a multiple of 4, but inputs that start 4 bytes past a 16-byte boundary take the 4-byte path: the
+    gradients have the bits of the aligned call (the same float32 operations per pixel), n_c is equal (a sum of float32 in
+    double: exact either way) and the sums stay within test_loss_kernel_vs_fp64's tolerance"""
+    from starst3r_amd import ops
+    C, H, W = 3, 16, 64
+    D, alpha, Z, w = _kernel_inputs(C, H, W)
+    s_ref, n_ref, _, _ = _kernel_ref(D, alpha, Z, w, DEPTH_FAC)
+
+    def off(t):
+        big = torch.zeros(t.numel() + 4, device="cuda:0")
+        out = big[1:1 + t.numel()].view(t.shape)
+        out.copy_(t)
+        assert out.data_ptr() % 16 == 4
+        return out
+    sums, v_d, v_a = ops.loss_depth_prior(ctx, *[x.cuda().contiguous() for x in (D, alpha, Z, w)], DEPTH_FAC)
+    sums_o, v_do, v_ao = ops.loss_depth_prior(ctx, *[off(x) for x in (D, alpha, Z, w)], DEPTH_FAC)
+    torch.cuda.synchronize()
+    assert _same_bits(v_do.clone(), v_d) and _same_bits(v_ao.clone(), v_a)
+    assert torch.equal(sums_o[:, 1], sums[:, 1])
+    np.testing.assert_allclose(sums_o[:, 1].cpu().numpy(), n_ref.numpy(), rtol=1e-12, atol=0)
+    zmax = float(Z[w > 0].max())
+    for c in range(C):
+        np.testing.assert_allclose(float(sums_o[c, 0]), float(s_ref[c]), rtol=1e-6, atol=1e-6 * zmax * float(n_ref[c]))
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # helpers of the fused-step tests
 # ---------------------------------------------------------------------------------------------------------------------
