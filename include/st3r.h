@@ -361,6 +361,9 @@ int st3r_gs_render(st3r_ctx* ctx, void* stream, int N, int C, const float* means
  *    8 level-1 sort: small tile shape   9 its items per tile   10 its tiles   11 tiles per segment (0: no segments)
  *      12 its passes (0 with segments)
  *   13 bits of the (camera, tile) key sorted   14 tile sort: small shape   15 items per tile   16 tiles   17 passes
+ *      (14 .. 17 describe the two-pass form also when the banded form below replaces it)
+ *   18 banded tile sort taken (keys of 9 .. 16 bits, debug flag 16 clear): the emission splits the records by the high
+ *      key byte and one low-byte pass per band is left   19 its bands   30 the tiles that pass is launched with
  *   20 SCAN_TILE  21 EP  22 ECH  23 EMIT_SELF_BASE_MAX  24 keys per thread of the offsets kernel  25 RS_SMALL_BELOW
  *   26 / 27 items per small / large sort tile, 32-bit keys   28 / 29 the same, 64-bit keys */
 #define ST3R_FRONT_PLAN_WORDS 32

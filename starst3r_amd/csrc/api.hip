@@ -94,11 +94,12 @@ int st3r_arena_get2(st3r_ctx* ctx, int slot, size_t bytes, void** out, int* grow
 // Debug/test hook: device pointer and capacity of a scratch buffer of the last fused step.
 // which: 0 = sorted pair ids ("flatten ids", int32 [n_isects]), 1 = tile offsets (int32 [C*tiles]),
 //        2 = splat records (float [C*N*12]), 3 = inclusive tile scan in pair-id order (int32 [C*N])
+//        11 / 12 = emitted tile keys / pair ids (the tile sort's input), 13 = sorted tile keys (uint32 / int32 [n_isects])
 ST3R_EXPORT int st3r_ctx_peek(st3r_ctx* ctx, void* stream, int which, void* dst, int64_t bytes) {
-    ARG_CHECK(ctx && dst && bytes >= 0 && which >= 0 && which <= 10);
-    static const int slots[11] = {SLOT_VALS_B, SLOT_OFFSETS, SLOT_SPLATS, SLOT_CUM,
+    ARG_CHECK(ctx && dst && bytes >= 0 && which >= 0 && which <= 13);
+    static const int slots[14] = {SLOT_VALS_B, SLOT_OFFSETS, SLOT_SPLATS, SLOT_CUM,
                                   SLOT_MCMC_CUM, SLOT_MCMC_DEAD, SLOT_MCMC_SAMPLED, SLOT_MCMC_COUNT,
-                                  SLOT_RGB, SLOT_ALPHA, SLOT_COUNTS};
+                                  SLOT_RGB, SLOT_ALPHA, SLOT_COUNTS, SLOT_KEYS_A, SLOT_VALS_A, SLOT_KEYS_B};
     ARG_CHECK((size_t)bytes <= ctx->slot_bytes[slots[which]]);
     HIP_TRY(hipMemcpyAsync(dst, ctx->slot_ptr[slots[which]], (size_t)bytes, hipMemcpyDeviceToDevice,
                            (hipStream_t)stream));
@@ -145,6 +146,14 @@ void st3r_prof_next_step(st3r_ctx* ctx) {
 ST3R_EXPORT int st3r_ctx_set_debug(st3r_ctx* ctx, int flags) {
     ARG_CHECK(ctx);
     ctx->debug_flags = flags;
+    // test hook, acts once when set: the next launch of either single-pass scan is the last one of its 14-bit status-word
+    // generation, the one after it clears its control block (gs_isect.hip: chain_ctl)
+    // (the two ticket counters of a scan take turns by generation parity, so the parity sequence is kept: two or three
+    // launches are left)
+    if (flags & 256) {
+        ctx->scan_gen = (ctx->scan_gen & 1u) ? 0x3FFDu : 0x3FFEu;
+        ctx->scan_gen_b = (ctx->scan_gen_b & 1u) ? 0x3FFDu : 0x3FFEu;
+    }
     return ST3R_OK;
 }
 

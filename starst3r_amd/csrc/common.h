@@ -87,6 +87,7 @@ enum ArenaSlot {
     SLOT_DPRIOR_NORM, // the same: n_c = max(sum w_c, 1) of every registered view, computed once per registration
     SLOT_DPRIOR_SUMS, // the same: sum_p w |ED - Z| per view of the fused step
     SLOT_EXPOSURE_PART, // exposure backward (gs_exposure.hip): one 12-double partial per (view, workgroup)
+    SLOT_SCAN_CHAIN_B, // the band-counter scan of the banded emission (gs_isect.hip): a control block of its own, so that no clear of it can touch the pair-order scan's total while the step still reads it
     SLOT_EXPOSED,     // fused step with exposures (fused_step.hip): the exposed image y [C,H,W,3] the loss reads (SLOT_RGB keeps the raw render)
     SLOT_COUNT
 };
@@ -145,7 +146,7 @@ struct st3r_ctx {
     int64_t* pinned;  // small pinned host buffer for read-backs
     // profiling: ring of (start, stop) events per stage; elapsed times are harvested lazily
     int debug_flags;  // st3r_ctx_set_debug: bit 0 = blend forward ignores the per-quadrant relevance test; 1: backward
-                      // recomputes the tile rectangles; 2 (4): level-1 sort on (camera | depth) keys in four passes; 3: async capacity halved; 5: training calls start at 2 view chunks;
+                      // recomputes the tile rectangles; 2 (4): level-1 sort on (camera | depth) keys in four passes; 3: async capacity halved; 4 (16): plain emission and two-pass tile sort instead of the banded form; 8 (256, acts when set): the scans' status-word generations jump to two or three launches before their wrap; 5: training calls start at 2 view chunks;
                       // 6: backward gathers rectangle and slot base separately; 7 (128): training forward on the quadrant
                       // kernel; 9 (512): st3r_gs_render on the cell-list kernel; 11 (2048): under a communicator
                       // st3r_gs_train_step behaves as if this rank's forward / backward had failed (comm.hip)
@@ -162,6 +163,7 @@ struct st3r_ctx {
     int bwd_stamp;  // generation stamp of the per-(record, tile) partial-gradient slots
     int depth_stamp;  // the same for the depth backward's slots (SLOT_VTILE_DEPTH)
     uint32_t scan_gen;   // single-pass scan (gs_isect.hip): generation of its status words
+    uint32_t scan_gen_b; // the same for the band-counter scan's own control block (SLOT_SCAN_CHAIN_B)
     // record count of the fused steps without a host round trip: sizing hint from the last known count, the read-back
     // still in flight (event), and the capacity the in-flight step was given
     int64_t isect_hint, count_cap;
@@ -208,6 +210,10 @@ int st3r_arena_get2(st3r_ctx* ctx, int slot, size_t bytes, void** out, int* grow
         if (_rc) return _rc;                                                                 \
         var = (type*)_p;                                                                     \
     }
+
+// the band table of the banded tile sort (gs_isect.hip: k_band_table writes it, radix_sort.hip reads it): two arrays of
+// this many words -- up to 256 band starts + the record count, up to 256 first sort tiles + the tiles in use
+#define ST3R_BAND_TAB 257
 
 static inline int ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 

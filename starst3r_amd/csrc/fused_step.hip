@@ -179,13 +179,21 @@ static int rasterize_front(st3r_ctx* ctx, hipStream_t s, const GsParams& g, cons
     // the sort and the offsets read the record count from device memory in both paths: the pair-order scan's total
     o->n_records = async ? -1 : n_isects;
     if (n_isects > 0) {
+        // Keys of 9 .. 16 bits: the emission writes the records split by the high byte of their key (the "band"), in
+        // (camera, depth) order inside every band, and ONE stable pass on the low byte inside every band is left of the
+        // tile sort -- the same (camera, tile, depth) order as the two passes (debug flag 16), bit for bit.
+        const int end_bit = fp.end_bit;
+        const bool banded = st3r_sort_tile_banded(end_bit, ctx->debug_flags) != 0;
+        const int n_bands = (int)(((int64_t)C * tile_w * tile_h - 1) >> 8) + 1;
+        const uint32_t* band_table = nullptr;
         st3r_prof_begin(ctx, s, STG_EMIT);
-        rc = st3r_isect_emit_chain_impl(ctx, s, N, C, perm, rects, rect32, tile_w, tile_h, tkeys_a, vals_a, n_isects);
+        rc = st3r_isect_emit_chain_impl(ctx, s, N, C, perm, rects, rect32, tile_w, tile_h, tkeys_a, vals_a, n_isects,
+                                        banded ? st3r_sort_tile_banded_tile(n_isects) : 0, total_dev, &band_table);
         st3r_prof_end(ctx, s, STG_EMIT);
         if (rc) return rc;
-        const int end_bit = fp.end_bit;
         st3r_prof_begin(ctx, s, STG_SORT);
-        rc = st3r_sort_tile_impl(ctx, s, n_isects, end_bit, tkeys_a, vals_a, tkeys_b, vals_b, total_dev);
+        rc = banded ? st3r_sort_tile_banded_impl(ctx, s, n_isects, n_bands, band_table, tkeys_a, vals_a, tkeys_b, vals_b)
+                    : st3r_sort_tile_impl(ctx, s, n_isects, end_bit, tkeys_a, vals_a, tkeys_b, vals_b, total_dev);
         st3r_prof_end(ctx, s, STG_SORT);
         if (rc) return rc;
     }
@@ -595,6 +603,13 @@ ST3R_EXPORT int st3r_front_plan(int N, int C, int width, int height, int debug_f
     if (n_records > 0) {
         st3r_radix_sort_shape(4, n_records, 0, 0, 0, (int)out[13], sh);
         out[14] = sh[0]; out[15] = sh[1]; out[16] = sh[2]; out[17] = sh[4];
+    }
+    // the banded form of the tile sort (words 14 .. 17 keep describing the two-pass form, which debug flag 16 selects):
+    // taken or not, its bands, and the tiles its one pass is launched with
+    if (st3r_sort_tile_banded(fp.end_bit, debug_flags)) {
+        out[18] = 1;
+        out[19] = (((int64_t)C * fp.tile_w * fp.tile_h - 1) >> 8) + 1;
+        if (n_records > 0) out[30] = n_records / st3r_sort_tile_banded_tile(n_records) + out[19];
     }
     int64_t k[5];
     st3r_isect_constants(k);

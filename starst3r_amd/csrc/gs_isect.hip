@@ -3,7 +3,8 @@
 //              isect_tiles passes): one single-pass kernel with decoupled look-back (k_scan_chained);
 //   emit    -- gsplat isect_tiles pass 2: one (key,value) per touched tile (k_isect_emit: the stage API's
 //              64-bit keys in pair order; k_isect_gather / k_isect_wg_scan / k_isect_emit_d: the fused
-//              path's 32-bit (camera, tile) keys in (camera, depth) order);
+//              path's 32-bit (camera, tile) keys in (camera, depth) order;
+//              k_band_table / k_isect_emit_b: the same records split by the high key byte, for the one-pass tile sort);
 //   offsets -- gsplat isect_offset_encode.
 // All integer work: results are bit-exact against oracle/gs_oracle.c.
 #include "stages.h"
@@ -193,16 +194,22 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_scan_chained(const int32_t* in
 // word per tile.  Nothing is cleared between launches (generation-stamped words, the ticket counters take turns); the
 // host clears the block when it is (re)allocated and when the 14-bit generation is about to repeat.
 struct ChainCtl { uint32_t* tickets; int32_t* total; u64* status; uint32_t gen; };
-static int chain_ctl(st3r_ctx* ctx, hipStream_t s, int64_t nwords, ChainCtl* c) {
+// A scan's total lives IN its control block, and a caller may read it on the device long after the scan (the record count of
+// a fused step: the emission, the band table, the sorts, the offsets).  A clear of the block wipes that total in stream
+// order, so a second scan inside the same step must not share the block: `band` selects the block and the generation
+// counter of the band-counter scan of the banded emission, every other scan uses the first one.
+static int chain_ctl(st3r_ctx* ctx, hipStream_t s, int64_t nwords, ChainCtl* c, bool band) {
+    const int slot = band ? SLOT_SCAN_CHAIN_B : SLOT_SCAN_CHAIN;
+    uint32_t* const gen = band ? &ctx->scan_gen_b : &ctx->scan_gen;
     void* p; int grown = 0;
-    int rc = st3r_arena_get2(ctx, SLOT_SCAN_CHAIN, sizeof(u64) * ((size_t)nwords + 16), &p, &grown);
+    int rc = st3r_arena_get2(ctx, slot, sizeof(u64) * ((size_t)nwords + 16), &p, &grown);
     if (rc) return rc;
-    if (grown || ctx->scan_gen >= 0x3FFF) {
-        HIP_TRY(hipMemsetAsync(p, 0, ctx->slot_bytes[SLOT_SCAN_CHAIN], s));
-        ctx->scan_gen = 0;
+    if (grown || *gen >= 0x3FFF) {
+        HIP_TRY(hipMemsetAsync(p, 0, ctx->slot_bytes[slot], s));
+        *gen = 0;
     }
     u64* ctl = (u64*)p;
-    c->gen = ++ctx->scan_gen;
+    c->gen = ++*gen;
     c->tickets = (uint32_t*)ctl;                           // ctl[0..3]
     c->total = (int32_t*)(ctl + 4) + (c->gen & 3);         // ctl[4..5]
     c->status = ctl + 16;
@@ -215,10 +222,10 @@ int st3r_scan_tiles(int64_t n) { return ceil_div(n, SCAN_TILE); }
 // device memory (*total_dev)
 static int st3r_scan_inclusive_i32(st3r_ctx* ctx, hipStream_t s, const int32_t* in, const void* rects, int rect32,
                                    int32_t* out, int64_t n, int32_t** total_dev, uint64_t* pack_out = nullptr,
-                                   int32_t* total_copy = nullptr, int32_t* total_host = nullptr) {
+                                   int32_t* total_copy = nullptr, int32_t* total_host = nullptr, bool band = false) {
     const int ntiles = st3r_scan_tiles(n);
     ChainCtl c;
-    int rc = chain_ctl(ctx, s, ntiles, &c);
+    int rc = chain_ctl(ctx, s, ntiles, &c, band);
     if (rc) return rc;
 #define SCAN_LAUNCH(R, P)                                                                                                \
     hipLaunchKernelGGL((k_scan_chained<R, P>), dim3(ntiles), dim3(SCAN_THREADS), 0, s, in, rects, rect32, n, out, pack_out, \
@@ -503,12 +510,35 @@ __device__ __forceinline__ void emit_item(int C, int bpc, int* c, int* k) {
     else { *c = b / bpc; *k = b % bpc; }
 }
 
+// The bands of the banded emission (described with k_isect_emit_b below): first band, band count and counter offset of
+// camera c -- the one place this arithmetic lives, for the counters, the table and the emission alike.
+struct BandLayout { int first, n; int64_t off; };   // first band, bands, cam_off of one camera
+__host__ __device__ __forceinline__ BandLayout band_layout(int c, int n_tiles, int bpc) {
+    BandLayout b;
+    int64_t nb = 0;
+    for (int i = 0; i < c; ++i) nb += ((int)(((int64_t)(i + 1) * n_tiles - 1) >> 8)) - ((int)(((int64_t)i * n_tiles) >> 8)) + 1;
+    b.first = (int)(((int64_t)c * n_tiles) >> 8);
+    b.n = (int)(((int64_t)(c + 1) * n_tiles - 1) >> 8) - b.first + 1;
+    b.off = nb * bpc;
+    return b;
+}
+
 __global__ __launch_bounds__(256) void k_isect_gather(int N, int C, int bpc, const int32_t* __restrict__ perm,
                                                       const void* __restrict__ rects, int rect32,
-                                                      void* __restrict__ rects_d, int32_t* __restrict__ wg_tiles) {
+                                                      void* __restrict__ rects_d, int32_t* __restrict__ wg_tiles,
+                                                      int tile_w, int n_tiles, int32_t* __restrict__ bcnt) {
+    // bcnt != NULL (banded emission, below): also the workgroup's records per band of its camera -- LDS integer adds, one
+    // per piece of a rectangle row inside one band
+    extern __shared__ uint32_t s_cnt[];
     int c, k;
     emit_item(C, bpc, &c, &k);
     const int t = threadIdx.x;
+    BandLayout bl = {0, 0, 0};
+    if (bcnt) {
+        bl = band_layout(c, n_tiles, bpc);
+        for (int b = t; b < bl.n; b += 256) s_cnt[b] = 0;
+        __syncthreads();
+    }
     const int64_t first = (int64_t)c * N + (int64_t)k * EP;
     const int np = (int)min((int64_t)EP, (int64_t)(c + 1) * N - first);
     int32_t pid[EPT];
@@ -519,20 +549,33 @@ __global__ __launch_bounds__(256) void k_isect_gather(int N, int C, int bpc, con
     for (int j = 0; j < EPT; ++j) {
         if (pid[j] >= 0) {
             const int64_t dst = first + j * 256 + t;
+            uint32_t org, rw, rh;   // origin x0 | y0 << 16, width, height: rect_load's decode of either form
             if (rect32) {
                 const uint32_t r = reinterpret_cast<const uint32_t*>(rects)[pid[j]];
                 reinterpret_cast<uint32_t*>(rects_d)[dst] = r;
-                sum += (int)((r >> 16) & 0xFFu) * (int)(r >> 24);
+                org = (r & 0xFFu) | ((r & 0xFF00u) << 8); rw = (r >> 16) & 0xFFu; rh = r >> 24;
             } else {
                 const uint64_t r = reinterpret_cast<const uint64_t*>(rects)[pid[j]];
                 reinterpret_cast<uint64_t*>(rects_d)[dst] = r;
-                sum += (int)((r >> 32) & 0xFFFF) * (int)(r >> 48);
+                org = (uint32_t)(r & 0xFFFFFFFFull); rw = (uint32_t)((r >> 32) & 0xFFFF); rh = (uint32_t)(r >> 48);
             }
+            sum += (int)rw * (int)rh;
+            if (bcnt && rw)
+                for (uint32_t ty = 0; ty < rh; ++ty) {
+                    uint32_t ka = (uint32_t)c * (uint32_t)n_tiles + ((org >> 16) + ty) * (uint32_t)tile_w + (org & 0xFFFF);
+                    for (uint32_t left = rw; left;) {   // (a row narrower than 256 tiles meets at most two bands)
+                        const uint32_t piece = min(left, ((ka >> 8) + 1u) * 256u - ka);
+                        atomicAdd(&s_cnt[(ka >> 8) - (uint32_t)bl.first], piece);
+                        ka += piece; left -= piece;
+                    }
+                }
         }
     }
     int total;
     block_incl_scan(sum, &total);
     if (t == 0) wg_tiles[c * bpc + k] = total;   // < 2^30: 1024 rectangles of < 2^20 tiles
+    if (bcnt)   // (block_incl_scan's barriers stand between the adds and these reads)
+        for (int b = t; b < bl.n; b += 256) bcnt[bl.off + (int64_t)b * bpc + k] = (int32_t)s_cnt[b];
 }
 
 // Exclusive prefix of the workgroup tile counts over ALL cameras, camera-major, as a launch of its own: only for grids of
@@ -697,6 +740,247 @@ __global__ __launch_bounds__(256) void k_isect_emit_d(int N, int C, int bpc, con
     }
 }
 
+// ------------------------------------------------------------------------------------
+// Banded emission (tile keys of 9 .. 16 bits): the records leave split by the HIGH byte of their (camera, tile) key, the
+// "band", in (camera, depth) order inside every band -- a stream that is already sorted on the high byte, so that ONE
+// stable radix pass on the low byte inside every band (radix_sort.hip: BAND) gives the (camera, tile, depth) order the
+// two-pass sort gave.  The write positions come from a count-and-scan done beforehand, not from a look-back:
+//   k_isect_gather   also counts the workgroup's records per band of its camera (bcnt != NULL): a rectangle row covers the
+//                    keys [key0 + ty tile_w + x0, + w), w < 256, which meet at most two bands;
+//   (one chained scan over the counters, band-major and then in workgroup order c * bpc + k -- see band_layout)
+//   k_band_table     band starts and lengths, the sort tiles of every band, the tiles in use;
+//   k_isect_emit_b   k_isect_emit_d's decode; inside a chunk a wave owns ECH_B / 4 consecutive outputs (rows of 64), lanes
+//                    of a row that share a band find each other with ballots (as many as the camera's band count needs
+//                    bits: 6 at 8 x 1080p), per-wave band counters in LDS, after the chunk's barrier an exclusive prefix
+//                    over the four waves and a running count per band across the chunks (a register of thread `band`);
+//                    the chunk is regrouped by band in LDS and leaves in runs that are contiguous in the destination
+//                    (stored straight from the ranking lanes a wave's 64 outputs meet ~20 of the 33 bands of a 1080p
+//                    camera, a dozen bytes per run: that form took twice the time of the plain emission).
+// A camera owns the bands first_band(c) = (c n_tiles) >> 8 .. ((c + 1) n_tiles - 1) >> 8; neighbouring cameras share a
+// band when n_tiles is no multiple of 256.  Counter of (camera c, local band j, workgroup k): cam_off(c) + j bpc + k with
+// cam_off(c) = bpc * (bands of the cameras in front) -- band-major, and camera-major inside a shared band.
+#ifndef ECH_B
+// outputs per chunk of the banded emission (a multiple of 512).  Measured at SYNTH-1M (emit stage, same box): 4096 -- 147
+// VGPRs, 38.9 KB of LDS, three workgroups per CU -- 0.254 ms; 2048 (95 VGPRs, 26.7 KB, five) 0.210; 1024 (71 VGPRs, 20.5 KB,
+// seven, as k_isect_emit_d) 0.194
+#define ECH_B 1024
+#endif
+__global__ __launch_bounds__(256) void k_isect_emit_b(int N, int C, int bpc, const int32_t* __restrict__ perm,
+                                                      const void* __restrict__ rects_d, int rect32,
+                                                      const int32_t* __restrict__ binc, int tile_w, int tile_h, int bits,
+                                                      uint32_t* __restrict__ tile_keys, int32_t* __restrict__ vals,
+                                                      int64_t cap) {
+    constexpr int ROWS = ECH_B / 256, NWV = ECH_B / 512;   // rows of 64 outputs per wave; 32-bit words of s_own per thread
+    __shared__ int s_end[EP];
+    __shared__ uint32_t s_org[EP];
+    __shared__ uint16_t s_w[EP];
+    __shared__ int32_t s_pid[EP];
+    __shared__ uint16_t s_own[ECH_B];
+    __shared__ uint32_t s_srt[ECH_B];   // the chunk regrouped by band: pair index << 16 | local band << 8 | low key byte
+    __shared__ unsigned s_wmax[4];
+    // per band of the camera (sized at the launch, 16 bytes a band): the chunk's first position minus its first regrouped
+    // index, that index, and the four waves' counters (uint16)
+    extern __shared__ uint32_t s_band[];
+    int c, k;
+    emit_item(C, bpc, &c, &k);
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const BandLayout bl = band_layout(c, tile_w * tile_h, bpc);
+    const int nbl = bl.n;
+    uint32_t* s_pos = s_band;
+    uint32_t* s_cst = s_band + nbl;
+    uint16_t* s_bc = reinterpret_cast<uint16_t*>(s_band + 2 * nbl);   // [4][nbl]
+    const int64_t first = (int64_t)c * N + (int64_t)k * EP;
+    const int np = (int)min((int64_t)EP, (int64_t)(c + 1) * N - first);
+    int cnt[EPT];
+#pragma unroll
+    for (int j = 0; j < EPT; ++j) {
+        const int e = j * 256 + t;
+        int32_t pid = 0;
+        uint32_t org = 0, rw = 0, rh = 0;
+        if (e < np) {
+            pid = perm[first + e];
+            rect_load(rects_d, rect32, first + e, &org, &rw, &rh);
+        }
+        s_pid[e] = pid; s_org[e] = org; s_w[e] = (uint16_t)rw;
+        cnt[j] = (int)(rw * rh);
+    }
+    int carry = 0;
+#pragma unroll
+    for (int j = 0; j < EPT; ++j) {
+        int tot;
+        const int inc = block_incl_scan(cnt[j], &tot);
+        s_end[j * 256 + t] = carry + inc;
+        carry += tot;
+    }
+    const int total = carry;
+    __syncthreads();
+    // thread b < nbl keeps the next free position of band b of this workgroup (nbl <= 256: keys of at most 16 bits)
+    uint32_t run = 0;
+    if (t < nbl) {
+        const int64_t idx = bl.off + (int64_t)t * bpc + k;
+        run = idx ? (uint32_t)binc[idx - 1] : 0u;
+    }
+    const uint32_t key0 = (uint32_t)c * (uint32_t)(tile_w * tile_h);
+    const u64 lt = (1ull << lane) - 1ull;
+    uint16_t* bc = s_bc + w * nbl;
+    int carry_owner = 0;
+    for (int c0 = 0; c0 < total; c0 += ECH_B) {
+#pragma unroll
+        for (int q = 0; q < NWV; ++q) reinterpret_cast<uint32_t*>(s_own)[t + 256 * q] = 0u;
+        for (int b = lane; b < nbl; b += 64) bc[b] = 0;
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < EPT; ++j) {
+            const int e = j * 256 + t;
+            if (e < np) {
+                const int start = e ? s_end[e - 1] : 0;
+                if (s_end[e] > start && start >= c0 && start < c0 + ECH_B) s_own[start - c0] = (uint16_t)(e + 1);
+            }
+        }
+        __syncthreads();
+        // prefix maximum of the marks, as in k_isect_emit_d: thread t owns 2 NWV consecutive entries
+        unsigned wv[NWV];
+#pragma unroll
+        for (int q = 0; q < NWV; ++q) wv[q] = reinterpret_cast<const uint32_t*>(s_own)[NWV * t + q];
+        unsigned runm = 0;
+#pragma unroll
+        for (int i = 0; i < NWV; ++i) {
+            const unsigned lo = max(runm, wv[i] & 0xFFFFu);
+            runm = max(lo, wv[i] >> 16);
+            wv[i] = lo | (runm << 16);
+        }
+        unsigned inc = runm;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const unsigned o = __shfl_up(inc, off);
+            if (lane >= off) inc = max(inc, o);
+        }
+        if (lane == 63) s_wmax[w] = inc;
+        unsigned excl_m = __shfl_up(inc, 1);
+        if (lane == 0) excl_m = 0;
+        __syncthreads();
+        unsigned pre = max((unsigned)carry_owner, excl_m);
+#pragma unroll
+        for (int ww = 0; ww < 4; ++ww)
+            if (ww < w) pre = max(pre, s_wmax[ww]);
+        carry_owner = (int)max(max(max((unsigned)carry_owner, s_wmax[0]), max(s_wmax[1], s_wmax[2])), s_wmax[3]);
+#pragma unroll
+        for (int i = 0; i < NWV; ++i) {
+            const unsigned lo = max(wv[i] & 0xFFFFu, pre), hi = max(wv[i] >> 16, pre);
+            wv[i] = lo | (hi << 16);
+        }
+#pragma unroll
+        for (int q = 0; q < NWV; ++q) reinterpret_cast<uint32_t*>(s_own)[NWV * t + q] = wv[q];
+        __syncthreads();
+        const int lim = min(ECH_B, total - c0);
+        // rank: wave w owns the outputs [w ECH_B / 4, (w + 1) ECH_B / 4) of the chunk, row by row;
+        // item = local band << 24 | low key byte << 16 | rank among the wave's records of that band in this chunk
+        uint32_t item[ROWS];
+#pragma unroll
+        for (int r = 0; r < ROWS; ++r) {
+            const int i = w * (ECH_B / 4) + r * 64 + lane;
+            const bool valid = i < lim;
+            uint32_t key = 0, band = 0;
+            if (valid) {
+                const int p = (int)s_own[i] - 1;
+                const int kk = c0 + i - (p == 0 ? 0 : s_end[p - 1]);
+                const uint32_t w_ = s_w[p], org = s_org[p];
+                // kk / w with kk < w * h <= 2^20 and w < 2^10: float estimate, corrected by one either way
+                int qq = (int)((float)kk * __builtin_amdgcn_rcpf((float)w_));
+                int rem = kk - qq * (int)w_;
+                if (rem < 0) { --qq; rem += (int)w_; }
+                if (rem >= (int)w_) { ++qq; rem -= (int)w_; }
+                key = key0 + ((org >> 16) + (uint32_t)qq) * (uint32_t)tile_w + (org & 0xFFFF) + (uint32_t)rem;
+                band = (key >> 8) - (uint32_t)bl.first;
+            }
+            u64 m = __ballot(valid);
+            for (int bb = 0; bb < bits; ++bb) {
+                const bool bit = (band >> bb) & 1u;
+                const u64 bal = __ballot(bit);
+                m &= bit ? bal : ~bal;
+            }
+            const uint32_t below = (uint32_t)__popcll(m & lt);
+            uint32_t prev = 0;
+            if (valid) {
+                prev = bc[band];
+                if (below == 0) bc[band] = (uint16_t)(prev + (uint32_t)__popcll(m));
+            }
+            item[r] = (band << 24) | ((key & 0xFFu) << 16) | (prev + below);
+        }
+        __syncthreads();
+        // per band: exclusive prefix over the waves (in place), the band's first regrouped index of this chunk (a scan over
+        // the bands), its first position, and the running count
+        uint32_t acc = 0;
+        if (t < nbl) {
+#pragma unroll
+            for (int ww = 0; ww < 4; ++ww) {
+                const uint32_t n = s_bc[ww * nbl + t];
+                s_bc[ww * nbl + t] = (uint16_t)acc;
+                acc += n;
+            }
+        }
+        int chunk_tot;
+        const uint32_t cst = (uint32_t)block_incl_scan((int)acc, &chunk_tot) - acc;
+        if (t < nbl) {
+            s_cst[t] = cst;
+            s_pos[t] = run - cst;
+            run += acc;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < ROWS; ++r) {
+            const int i = w * (ECH_B / 4) + r * 64 + lane;
+            if (i < lim) {
+                const uint32_t band = item[r] >> 24;
+                s_srt[s_cst[band] + bc[band] + (item[r] & 0xFFFFu)] = (((uint32_t)s_own[i] - 1u) << 16) | ((item[r] >> 16) & 0xFFFFu);
+            }
+        }
+        __syncthreads();
+        // regrouped index i of the chunk leaves for s_pos[band] + i: runs that are contiguous in the destination
+        for (int i = t; i < lim; i += 256) {
+            const uint32_t v = s_srt[i], band = (v >> 8) & 0xFFu;
+            const uint32_t pos = s_pos[band] + (uint32_t)i;
+            if ((int64_t)pos < cap) {
+                tile_keys[pos] = (((uint32_t)bl.first + band) << 8) | (v & 0xFFu);
+                vals[pos] = s_pid[v >> 16];
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// Band starts and the sort tiles of the one low-byte pass (radix_sort.hip: BAND), from the scanned counters.  table:
+// [0, 257) first position of every band, entry n_bands = the record count; [257, 514) first sort tile of every band, entry
+// n_bands = the tiles in use.  Every position is clamped to the capacity and to the record count (an overflowing step drops
+// records in the emission: the pass then sorts what was written, nothing past it), and a scan that wrapped (total < 0)
+// leaves no tile at all.
+__global__ __launch_bounds__(256) void k_band_table(int C, int n_tiles, int bpc, const int32_t* __restrict__ binc,
+                                                    int64_t n_cnt, const int32_t* __restrict__ scan_total,
+                                                    const int32_t* __restrict__ n_dev, int64_t cap, int sort_tile,
+                                                    uint32_t* __restrict__ table) {
+    __shared__ uint32_t s_start[ST3R_BAND_TAB];
+    const int t = threadIdx.x;
+    const int nb = (int)(((int64_t)C * n_tiles - 1) >> 8) + 1;
+    int64_t lim = cap;
+    if (n_dev) lim = min(lim, (int64_t)max(*n_dev, 0));
+    if (*scan_total < 0) lim = 0;
+    if (t < nb) {
+        int c = 0;
+        while ((int)(((int64_t)(c + 1) * n_tiles - 1) >> 8) < t) ++c;   // the first camera that owns band t
+        const BandLayout bl = band_layout(c, n_tiles, bpc);
+        const int64_t idx = bl.off + (int64_t)(t - bl.first) * bpc;
+        s_start[t] = (uint32_t)min((int64_t)(idx ? (uint32_t)binc[idx - 1] : 0u), lim);
+    }
+    if (t == 0) s_start[nb] = (uint32_t)min((int64_t)(uint32_t)binc[n_cnt - 1], lim);
+    __syncthreads();
+    uint32_t tiles = 0;
+    if (t < nb) tiles = (s_start[t + 1] - s_start[t] + (uint32_t)sort_tile - 1u) / (uint32_t)sort_tile;
+    int tot;
+    const int inc = block_incl_scan((int)tiles, &tot);
+    if (t < nb) { table[t] = s_start[t]; table[ST3R_BAND_TAB + t] = (uint32_t)inc - tiles; }
+    if (t == 0) { table[nb] = s_start[nb]; table[ST3R_BAND_TAB + nb] = (uint32_t)tot; }
+}
+
 // the emission grid: workgroups per camera, workgroups in all, and whether every workgroup sums its own base (no scan launch)
 void st3r_emit_grid(int N, int C, int* bpc, int* grid, int* self_base) {
     *bpc = ceil_div(N, EP);
@@ -708,8 +992,11 @@ void st3r_isect_constants(int64_t out[5]) {
     out[0] = SCAN_TILE; out[1] = EP; out[2] = ECH; out[3] = EMIT_SELF_BASE_MAX; out[4] = OFFSET_KEYS;
 }
 
+// band_tile > 0: the banded emission for a sort tile of that many items; *band_table then receives the table of
+// k_band_table (device memory, valid until the next call), n_dev is the record count on the device
 int st3r_isect_emit_chain_impl(st3r_ctx* ctx, hipStream_t s, int N, int C, const int32_t* perm, const void* rects,
-                               int rect32, int tile_w, int tile_h, uint32_t* tile_keys, int32_t* vals, int64_t cap) {
+                               int rect32, int tile_w, int tile_h, uint32_t* tile_keys, int32_t* vals, int64_t cap,
+                               int band_tile, const int32_t* n_dev, const uint32_t** band_table) {
     const int64_t n_pairs = (int64_t)N * C;
     if (n_pairs == 0) return ST3R_OK;
     int bpc, grid, self_base_i;
@@ -718,12 +1005,41 @@ int st3r_isect_emit_chain_impl(st3r_ctx* ctx, hipStream_t s, int N, int C, const
     int rc = st3r_arena_get(ctx, SLOT_RECTS_D, (rect32 ? sizeof(uint32_t) : sizeof(uint64_t)) * (size_t)n_pairs, &p);
     if (rc) return rc;
     void* rects_d = p;
-    rc = st3r_arena_get(ctx, SLOT_CUM_D, (sizeof(long long) + sizeof(int32_t)) * (size_t)grid + 16, &p);
+    // banded: one counter per (camera, band of the camera, workgroup), and the band table behind them
+    const int n_tiles = tile_w * tile_h;
+    int64_t n_cnt = 0;
+    int nbl_max = 0;
+    if (band_tile > 0) {
+        const BandLayout end = band_layout(C, n_tiles, bpc);
+        n_cnt = end.off;
+        for (int c = 0; c < C; ++c) nbl_max = std::max(nbl_max, band_layout(c, n_tiles, bpc).n);
+    }
+    const size_t wg_bytes = ((sizeof(long long) + sizeof(int32_t)) * (size_t)grid + 16 + 15) & ~(size_t)15;
+    rc = st3r_arena_get(ctx, SLOT_CUM_D, wg_bytes + sizeof(int32_t) * ((size_t)n_cnt + 2 * ST3R_BAND_TAB), &p);
     if (rc) return rc;
     long long* wg_base = (long long*)p;
     int32_t* wg_tiles = (int32_t*)(wg_base + grid);   // (8-byte entries in front: 16-byte aligned for even grids -- see below)
     if (((uintptr_t)wg_tiles & 15) != 0) wg_tiles += 2;
-    hipLaunchKernelGGL(k_isect_gather, dim3(grid), dim3(256), 0, s, N, C, bpc, perm, rects, rect32, rects_d, wg_tiles);
+    int32_t* bcnt = (int32_t*)((char*)p + wg_bytes);
+    uint32_t* table = (uint32_t*)(bcnt + n_cnt);
+    if (band_tile > 0) {
+        hipLaunchKernelGGL(k_isect_gather, dim3(grid), dim3(256), sizeof(uint32_t) * (size_t)nbl_max, s, N, C, bpc, perm, rects,
+                           rect32, rects_d, wg_tiles, tile_w, n_tiles, bcnt);
+        LAUNCH_CHECK();
+        int32_t* scan_total = nullptr;
+        // in place, with a control block of its own: n_dev points into the pair-order scan's (see chain_ctl)
+        rc = st3r_scan_inclusive_i32(ctx, s, bcnt, nullptr, 0, bcnt, n_cnt, &scan_total, nullptr, nullptr, nullptr, true);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_band_table, dim3(1), dim3(256), 0, s, C, n_tiles, bpc, bcnt, n_cnt, scan_total, n_dev, cap,
+                           band_tile, table);
+        hipLaunchKernelGGL(k_isect_emit_b, dim3(grid), dim3(256), 16 * (size_t)nbl_max, s, N, C, bpc, perm, rects_d, rect32,
+                           bcnt, tile_w, tile_h, bit_length_u32((uint32_t)(nbl_max - 1)), tile_keys, vals, cap);
+        LAUNCH_CHECK();
+        *band_table = table;
+        return ST3R_OK;
+    }
+    hipLaunchKernelGGL(k_isect_gather, dim3(grid), dim3(256), 0, s, N, C, bpc, perm, rects, rect32, rects_d, wg_tiles, tile_w,
+                       n_tiles, (int32_t*)nullptr);
     const bool self_base = self_base_i != 0;
     if (!self_base) hipLaunchKernelGGL(k_isect_wg_scan, dim3(1), dim3(1024), 0, s, grid, wg_tiles, wg_base);
     hipLaunchKernelGGL(k_isect_emit_d, dim3(grid), dim3(256), 0, s, N, C, bpc, perm, rects_d, rect32,

@@ -26,6 +26,15 @@ int st3r_sort_tile_impl(st3r_ctx* ctx, hipStream_t s, int64_t n, int end_bit, ui
     return st3r_radix_sort_u32(ctx, s, n, 0, end_bit, keys_in, vals_in, keys_out, vals_out);
 }
 
+// Banded form: the emission has split the records by the high byte of their key (gs_isect.hip), one low-byte pass is left.
+// Keys of at most 8 bits have one pass anyway, keys above 16 bits more than 256 bands: both keep the passes above.
+int st3r_sort_tile_banded(int end_bit, int debug_flags) { return end_bit > 8 && end_bit <= 16 && !(debug_flags & 16); }
+int st3r_sort_tile_banded_tile(int64_t n) { return st3r_radix_sort_band_tile(n); }
+int st3r_sort_tile_banded_impl(st3r_ctx* ctx, hipStream_t s, int64_t n, int n_bands, const uint32_t* band_table,
+                               uint32_t* keys_in, int32_t* vals_in, uint32_t* keys_out, int32_t* vals_out) {
+    return st3r_radix_sort_u32_banded(ctx, s, n, n_bands, band_table, keys_in, vals_in, keys_out, vals_out);
+}
+
 ST3R_EXPORT int st3r_gs_sort(st3r_ctx* ctx, void* stream, int64_t n_isects, int end_bit, int64_t* isect_ids,
                              int32_t* flatten_ids, int64_t* isect_ids_sorted, int32_t* flatten_ids_sorted) {
     ARG_CHECK(ctx && n_isects >= 0 && end_bit > 0);

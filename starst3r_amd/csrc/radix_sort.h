@@ -23,3 +23,9 @@ int st3r_radix_sort_u32_segments(st3r_ctx* ctx, hipStream_t s, int64_t seg_n, in
 // tiles per segment (seg_n > 0: n_seg segments of seg_n items), passes (0 for segments: decided on the device), then the
 // constants RS_SMALL_BELOW and the items per tile of the small and the large shape.  Computed by the code that launches.
 void st3r_radix_sort_shape(int key_bytes, int64_t n, int64_t seg_n, int n_seg, int begin_bit, int end_bit, int64_t out[8]);
+// One stable pass on the low key byte inside every band of a stream that is already split by the high byte (the banded
+// emission of gs_isect.hip).  band_table (device): n_bands + 1 band starts, the last one the item count, then from word ST3R_BAND_TAB
+// the first sort tile of every band and the tiles in use, for tiles of st3r_radix_sort_band_tile(n_cap) items.
+int st3r_radix_sort_band_tile(int64_t n_cap);
+int st3r_radix_sort_u32_banded(st3r_ctx* ctx, hipStream_t s, int64_t n_cap, int n_bands, const uint32_t* band_table,
+                               const uint32_t* keys_in, const int32_t* vals_in, uint32_t* keys_out, int32_t* vals_out);

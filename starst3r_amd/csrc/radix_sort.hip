@@ -16,6 +16,8 @@
 //                    protocol is independent of XCD placement); tiles are handed out by an atomic ticket so that
 //                    every predecessor of a running tile is itself running.  Items are regrouped by digit in LDS
 //                    and leave in runs that are contiguous in the destination.
+//   k_rs_hist_band / k_rs_pass<.., BAND>   the level-2 sort behind the banded emission (gs_isect.hip): the stream is already
+//                    split by the high key byte, one stable low-byte pass inside every band is all that is left.
 // Traffic per pass: one read and one write of keys and values (+ 2 KB of status words per tile).
 #include "radix_sort.h"
 
@@ -158,7 +160,14 @@ __global__ __launch_bounds__(HIST_THREADS) void k_rs_hist_seg(const uint32_t* __
 // by the projection's reduction from the depth range it saw: three when the biased keys stay below 2^24, else four): launch
 // `ps` returns at once when ps >= passes, and source / destination of a pass follow from the pass count so that the last
 // pass that runs writes kout / vout (kin = the caller's input, ktmp / vtmp = scratch).
-template <typename K, int THREADS, int IPT, bool SEG = false>
+// BAND (the level-2 sort behind the banded emission; K = uint32_t): the input is already split by the high key byte into
+// n_bands bands of any length; band_tab holds their starts (entry n_bands = the item count) and, from word BAND_TAB on, the
+// first tile of every band and the tiles in use.  A ticketed tile finds its band by a search over the first tiles (the
+// table travels through LDS), the chained scan restarts at the band's first tile, hist_base + 256 band is the band's own
+// low-byte histogram, and one pass on bits [0, 8) writes the caller's output.  The grid is sized for the capacity
+// (n / TILE + n_bands tiles); tickets past the tiles in use return at once.
+constexpr int BAND_TAB = ST3R_BAND_TAB;
+template <typename K, int THREADS, int IPT, bool SEG = false, bool BAND = false>
 __global__ __launch_bounds__(THREADS) void k_rs_pass(const K* __restrict__ kin, const int32_t* __restrict__ vin,
                                                      K* __restrict__ kout, int32_t* __restrict__ vout, int64_t n,
                                                      int shift, int bits, const uint32_t* __restrict__ hist_base,
@@ -166,7 +175,9 @@ __global__ __launch_bounds__(THREADS) void k_rs_pass(const K* __restrict__ kin, 
                                                      const int32_t* __restrict__ n_dev, int64_t seg_n = 0,
                                                      int tiles_per_seg = 0, const uint32_t* __restrict__ krange = nullptr,
                                                      int ps = 0, K* __restrict__ ktmp = nullptr,
-                                                     int32_t* __restrict__ vtmp = nullptr) {
+                                                     int32_t* __restrict__ vtmp = nullptr,
+                                                     const uint32_t* __restrict__ band_tab = nullptr, int n_bands = 0) {
+    static_assert(!(SEG && BAND), "one kind of segment per launch");
     if (n_dev) n = min(n, (int64_t)max(*n_dev, 0));   // count on the device, grid sized for the capacity `n`
     constexpr int TILE = THREADS * IPT, WAVES = THREADS / 64;
     uint32_t kmin = 0, ktop = 0;
@@ -194,9 +205,11 @@ __global__ __launch_bounds__(THREADS) void k_rs_pass(const K* __restrict__ kin, 
     __shared__ uint32_t wsum[4];
     __shared__ uint32_t hsum[4];
     __shared__ uint32_t s_tile;
+    __shared__ uint32_t s_btile[BAND ? BAND_TAB : 1];   // BAND: first tile of every band, [n_bands] = tiles in use
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     if (tid == 0) s_tile = atomicAdd(tile_counter, 1u);
     for (int i = tid; i < WAVES * RADIX; i += THREADS) (&whist[0][0])[i] = 0;
+    if constexpr (BAND) { if (tid <= n_bands) s_btile[tid] = band_tab[BAND_TAB + tid]; }
     __syncthreads();
     const uint32_t tile = s_tile;
     uint32_t first_tile = 0;      // first tile of this tile's chain (SEG: of its segment)
@@ -210,6 +223,19 @@ __global__ __launch_bounds__(THREADS) void k_rs_pass(const K* __restrict__ kin, 
         tbase = seg_base + in_seg;
         tcount = (int)min((int64_t)TILE, seg_n - in_seg);
         hist_base += (size_t)sg * (MAX_PASSES * RADIX);
+    } else if constexpr (BAND) {
+        if (tile >= s_btile[n_bands]) return;   // a ticket past the tiles in use: uniform over the workgroup
+        int lo = 0, hi = n_bands;               // the band with first tile <= tile < next first tile (empty bands have no tile)
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (s_btile[mid] <= tile) lo = mid; else hi = mid;
+        }
+        first_tile = s_btile[lo];
+        seg_base = (int64_t)band_tab[lo];
+        const int64_t in_band = (int64_t)(tile - first_tile) * TILE;
+        tbase = seg_base + in_band;
+        tcount = (int)min((int64_t)TILE, (int64_t)band_tab[lo + 1] - seg_base - in_band);
+        hist_base += (size_t)lo * RADIX;
     } else {
         if ((int64_t)tile * TILE >= n) return;   // (capacity launch) a ticket past the last tile: uniform over the workgroup
         tbase = (int64_t)tile * TILE;
@@ -233,7 +259,7 @@ __global__ __launch_bounds__(THREADS) void k_rs_pass(const K* __restrict__ kin, 
     // first pass: 4.6 us twice per step).
     uint32_t hv = 0;
     if (tid < RADIX) {
-        if constexpr (SEG) hv = hist_base[tid];   // (one histogram per segment)
+        if constexpr (SEG || BAND) hv = hist_base[tid];   // (one histogram per segment / band)
         else {
 #pragma unroll
             for (int c = 0; c < HIST_COPIES; ++c) hv += hist_base[c * (MAX_PASSES * RADIX) + tid];
@@ -383,6 +409,18 @@ SortShape sort_shape(int64_t n, int64_t seg_n = 0, int n_seg = 0) {
     sh.ntiles = seg_n > 0 ? (int64_t)sh.tiles_per_seg * n_seg : (n + sh.tile - 1) / sh.tile;
     return sh;
 }
+// The shape of the one banded pass (below): the rule above unless RS_BAND_SMALL_BELOW says otherwise.  Measured at SYNTH-1M
+// (26 M records, 255 bands): see tools/experiments/README.md, round 7.
+#ifndef RS_BAND_SMALL_BELOW
+#define RS_BAND_SMALL_BELOW RS_SMALL_BELOW
+#endif
+inline SortShape band_shape(int64_t n) {
+    constexpr int TILE_L = THREADS_L * Traits<uint32_t>::IPT, TILE_S = THREADS_S * Traits<uint32_t>::IPT_S;
+    SortShape sh = sort_shape<uint32_t>(n);
+    sh.small = (n + TILE_L - 1) / TILE_L < RS_BAND_SMALL_BELOW;
+    sh.tile = sh.small ? TILE_S : TILE_L;
+    return sh;
+}
 inline int sort_passes(int begin_bit, int end_bit) { return (end_bit - begin_bit + RB - 1) / RB; }
 
 template <typename K>
@@ -476,7 +514,94 @@ int sort_pairs_seg(st3r_ctx* ctx, hipStream_t s, int64_t seg_n, int n_seg, const
     return ST3R_OK;
 }
 
+// Low-byte histogram of every band of a banded stream: workgroup g owns the contiguous range [g per, (g + 1) per) of the
+// stream (not a grid stride), walks the bands that meet it -- one or two when the bands are longer than a range -- and
+// flushes 256 counters per band it saw.  hist: [n_bands][256].
+__global__ __launch_bounds__(HIST_THREADS) void k_rs_hist_band(const uint32_t* __restrict__ keys, int64_t per,
+                                                               const uint32_t* __restrict__ band_tab, int n_bands,
+                                                               uint32_t* __restrict__ hist) {
+    __shared__ uint32_t sh[HIST_THREADS / 64][RADIX];
+    __shared__ uint32_t s_start[BAND_TAB];
+    for (int i = threadIdx.x; i <= n_bands; i += HIST_THREADS) s_start[i] = band_tab[i];
+    __syncthreads();
+    const int64_t n = s_start[n_bands];
+    const int64_t r0 = (int64_t)blockIdx.x * per, r1 = min(r0 + per, n);
+    if (r0 >= r1) return;   // uniform
+    int lo = 0, hi = n_bands;   // the last band that starts at or before r0 (empty bands in front of it are skipped below)
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if ((int64_t)s_start[mid] <= r0) lo = mid; else hi = mid;
+    }
+    uint32_t* mine = sh[threadIdx.x >> 6];
+    constexpr int CH = HIST_THREADS * HIST_ITEMS;
+    for (int b = lo; b < n_bands && (int64_t)s_start[b] < r1; ++b) {
+        const int64_t a0 = max(r0, (int64_t)s_start[b]), a1 = min(r1, (int64_t)s_start[b + 1]);
+        if (a0 >= a1) continue;   // uniform
+        for (int i = threadIdx.x; i < (HIST_THREADS / 64) * RADIX; i += HIST_THREADS) (&sh[0][0])[i] = 0;
+        __syncthreads();
+        for (int64_t base = a0; base < a1; base += CH) {
+            uint32_t k[HIST_ITEMS];
+#pragma unroll
+            for (int i = 0; i < HIST_ITEMS; ++i) {
+                const int64_t idx = base + i * HIST_THREADS + threadIdx.x;
+                k[i] = idx < a1 ? keys[idx] : 0u;
+            }
+#pragma unroll
+            for (int i = 0; i < HIST_ITEMS; ++i)
+                if (base + i * HIST_THREADS + threadIdx.x < a1) atomicAdd(&mine[k[i] & (RADIX - 1)], 1u);
+        }
+        __syncthreads();
+        for (int i = threadIdx.x; i < RADIX; i += HIST_THREADS) {
+            uint32_t t = 0;
+#pragma unroll
+            for (int w = 0; w < HIST_THREADS / 64; ++w) t += sh[w][i];
+            if (t) atomicAdd(&hist[(size_t)b * RADIX + i], t);
+        }
+        __syncthreads();
+    }
+}
+
+int sort_pairs_banded(st3r_ctx* ctx, hipStream_t s, int64_t n, int n_bands, const uint32_t* band_tab, const uint32_t* keys_in,
+                      const int32_t* vals_in, uint32_t* keys_out, int32_t* vals_out) {
+    if (n == 0) return ST3R_OK;
+    typedef uint32_t K;
+    if (n_bands < 1 || n_bands > BAND_TAB - 1) { st3r_set_error("banded radix sort: 1 .. 256 bands"); return ST3R_ERR_INVALID; }
+    const SortShape sh = band_shape(n);
+    const int64_t ntiles = n / sh.tile + n_bands;   // every band may end in a ragged tile
+    const size_t hist_bytes = align256(sizeof(uint32_t) * ((size_t)n_bands * RADIX + MAX_PASSES));
+    const size_t status_bytes = sizeof(u64) * (size_t)ntiles * RADIX;
+    const size_t meta_bytes = hist_bytes + align256(status_bytes);
+    ARENA_GET(SLOT_SORT_TMP, char, meta_bytes, base);
+    uint32_t* hist = (uint32_t*)base;
+    uint32_t* counters = hist + (size_t)n_bands * RADIX;
+    u64* status = (u64*)(base + hist_bytes);
+    HIP_TRY(hipMemsetAsync(base, 0, meta_bytes, s));
+    constexpr int CH = HIST_THREADS * HIST_ITEMS;
+    // (2048 ranges: with 1024 a workgroup walked eight 4096-key chunks plus the ragged ones at its band edges, one latency
+    // after the other: 72 us at 26 M keys)
+    const int hist_blocks = (int)std::min<int64_t>(2048, (n + CH - 1) / CH);
+    const int64_t per = ((n + hist_blocks - 1) / hist_blocks + CH - 1) / CH * CH;
+    hipLaunchKernelGGL(k_rs_hist_band, dim3(hist_blocks), dim3(HIST_THREADS), 0, s, keys_in, per, band_tab, n_bands, hist);
+    if (sh.small)
+        hipLaunchKernelGGL((k_rs_pass<K, THREADS_S, Traits<K>::IPT_S, false, true>), dim3((unsigned)ntiles), dim3(THREADS_S), 0, s,
+                           keys_in, vals_in, keys_out, vals_out, n, 0, RB, hist, status, counters, (const int32_t*)nullptr,
+                           (int64_t)0, 0, (const uint32_t*)nullptr, 0, (K*)nullptr, (int32_t*)nullptr, band_tab, n_bands);
+    else
+        hipLaunchKernelGGL((k_rs_pass<K, THREADS_L, Traits<K>::IPT, false, true>), dim3((unsigned)ntiles), dim3(THREADS_L), 0, s,
+                           keys_in, vals_in, keys_out, vals_out, n, 0, RB, hist, status, counters, (const int32_t*)nullptr,
+                           (int64_t)0, 0, (const uint32_t*)nullptr, 0, (K*)nullptr, (int32_t*)nullptr, band_tab, n_bands);
+    LAUNCH_CHECK();
+    return ST3R_OK;
+}
+
 }  // namespace
+
+int st3r_radix_sort_band_tile(int64_t n_cap) { return (int)band_shape(n_cap).tile; }
+
+int st3r_radix_sort_u32_banded(st3r_ctx* ctx, hipStream_t s, int64_t n_cap, int n_bands, const uint32_t* band_table,
+                               const uint32_t* keys_in, const int32_t* vals_in, uint32_t* keys_out, int32_t* vals_out) {
+    return sort_pairs_banded(ctx, s, n_cap, n_bands, band_table, keys_in, vals_in, keys_out, vals_out);
+}
 
 void st3r_radix_sort_shape(int key_bytes, int64_t n, int64_t seg_n, int n_seg, int begin_bit, int end_bit, int64_t out[8]) {
     if (end_bit > 8 * key_bytes) end_bit = 8 * key_bytes;
