@@ -292,6 +292,45 @@ int st3r_exposure_adam_step(st3r_ctx* ctx, void* stream, int C, float* exposure,
 int st3r_ctx_set_exposure(st3r_ctx* ctx, const float* gt, const float* exposure, float* v_exposure, int C, int height,
                           int width);
 
+/* Gradient of the render loss with respect to each camera's intrinsics, from the per-pair gradients v_splats of
+ * st3r_gs_blend_bwd (floats 0-1 and 3-5; colour and depth do not depend on K): v_Ks [C,4] = d loss / d (fx, fy, cx, cy),
+ * written whole.  Per visible pair (radius > 0), in float32, with p = R m + t = (x, y, z), the projection Jacobian
+ * J = [[fx/z, 0, cj], [0, fy/z, d]], cj = -fx tx / z^2, tx = z clamp(x/z, -(0.15 W + cx)/fx, (1.15 W - cx)/fx), and v_J
+ * the gradient of J through the conic:
+ *   v_fx += v_mean2d.x x/z + v_J00 / z + v_J02 dcj/dfx        v_cx += v_mean2d.x + v_J02 dcj/dcx        (y alike)
+ * dcj/dfx = -x/z^2, dcj/dcx = 0 for an unclamped pair; 0 and 1/z for a clamped one, whose limit depends on K: the
+ * gradient of the forward as computed.  Tile rectangles and culling are not differentiated.  Sums in double in a fixed
+ * order (one partial per camera and block of 256 Gaussians, one finishing workgroup per camera), no atomics: the same
+ * inputs give the same bits.  A camera without a visible pair, and N == 0, get exact zeros. */
+int st3r_gs_intrinsics_bwd(st3r_ctx* ctx, void* stream, int N, int C, const float* means, const float* quats,
+                           const float* scales, const float* viewmats, const float* Ks, int width, int height,
+                           float eps2d, const float* splats, const float* v_splats, float* v_Ks);
+
+/* One Adam step on the intrinsics, on the device: Ks [C,3,3] (in/out), moments k_m, k_v [C,4] float32 (in/out), from
+ * v_Ks [C,4] (st3r_gs_intrinsics_bwd).  The parameters are q = (log fx, log fy, cx / width, cy / height), so one learning
+ * rate serves every image size: g = (fx v_fx, fy v_fy, width v_cx, height v_cy); torch's formulas in double, bias
+ * corrected by the 1-based `step`: delta = -lr mhat / (sqrt(vhat) + eps);  fx <- fx exp(delta_0), fy <- fy exp(delta_1),
+ * cx <- cx + width delta_2, cy <- cy + height delta_3.  mode bit 0: the focals are tied -- one scalar with gradient
+ * g_0 + g_1 and moment slot 0, both focals take the same factor, slot 1 keeps its bits; bit 1: the principal point is
+ * trained -- without it cx, cy and moment slots 2, 3 keep their bits.  Skew and row 2 of K are never written.  mask (may
+ * be NULL): [C] floats, a view with mask[c] == 0 keeps K, m and v bit for bit.  Guarded on the device like
+ * st3r_pose_adam_step: an asynchronous training step that outgrew its buffers moves no K.  Non-finite gradients are not
+ * filtered. */
+int st3r_intrinsics_adam_step(st3r_ctx* ctx, void* stream, int C, float* Ks, const float* v_Ks, float* k_m, float* k_v,
+                              double lr, double beta1, double beta2, double eps, int step, const float* mask, int width,
+                              int height, int mode);
+
+/* Registers, for the images at `gt` [C,H,W,3], the buffer v_Ks [C,4] that receives d loss / d (fx, fy, cx, cy).  From
+ * then on st3r_gs_train_fwd_bwd / _step / _step_poses whose ground-truth pointer is `gt` or a whole-view offset into it
+ * (view chunks) with the same height and width materialise the per-pair gradients as they do for the pose gradient
+ * (with a depth prior: the summed ones) and run st3r_gs_intrinsics_bwd on them behind their other launches; it writes
+ * the rows of v_Ks that belong to the call's views -- the kernels of the unfused chain, so the same bits.  Everything
+ * else the call computes is unchanged; with no registration every call runs exactly the launches it ran before.  The
+ * buffer stays the CALLER's (update the intrinsics between calls, e.g. with st3r_intrinsics_adam_step on the same
+ * stream); gt = NULL (or v_Ks = NULL) clears the registration.  st3r_gs_raster_train ignores it; with a communicator
+ * attached the training calls return ST3R_ERR_INVALID while a registration applies. */
+int st3r_ctx_set_intrinsics_grad(st3r_ctx* ctx, const float* gt, float* v_Ks, int C, int height, int width);
+
 /* fused Adam over the 23 active scalars per gaussian (replaces the 6 torch.optim.Adam of
  * starster/gs.py:37,159-161; sh0 and SH rows 4..23 never receive gradient and are
  * left untouched, their Adam update is exactly 0).  `step` is 1-based. */

@@ -52,6 +52,9 @@ SIGNATURES = {
     "st3r_exposure_bwd": [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp],
     "st3r_exposure_adam_step": [vp, vp, i32, vp, vp, vp, vp, f64, f64, f64, f64, i32, vp],
     "st3r_ctx_set_exposure": [vp, vp, vp, vp, i32, i32, i32],
+    "st3r_gs_intrinsics_bwd": [vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, i32, f32, vp, vp, vp],
+    "st3r_intrinsics_adam_step": [vp, vp, i32, vp, vp, vp, vp, f64, f64, f64, f64, i32, vp, i32, i32, i32],
+    "st3r_ctx_set_intrinsics_grad": [vp, vp, vp, i32, i32, i32],
     "st3r_adam_step": [vp, vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, f64, f64, f64, f64, i32],
     "st3r_adam_step_range": [vp, vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, f64, f64, f64, f64, i32, i64, i64, vp],
     "st3r_params_from_stage": [vp, vp, i32, vp, vp, vp, vp, vp, i32, vp, i64, i64, i64],

@@ -89,6 +89,7 @@ enum ArenaSlot {
     SLOT_EXPOSURE_PART, // exposure backward (gs_exposure.hip): one 12-double partial per (view, workgroup)
     SLOT_SCAN_CHAIN_B, // the band-counter scan of the banded emission (gs_isect.hip): a control block of its own, so that no clear of it can touch the pair-order scan's total while the step still reads it
     SLOT_EXPOSED,     // fused step with exposures (fused_step.hip): the exposed image y [C,H,W,3] the loss reads (SLOT_RGB keeps the raw render)
+    SLOT_KGRAD_PART,  // intrinsics backward (gs_intrinsics.hip): one 4-double partial per (camera, block of 256 Gaussians)
     SLOT_COUNT
 };
 
@@ -160,6 +161,8 @@ struct st3r_ctx {
     ViewReg dp; const float* dp_depth; const float* dp_weight; float dp_fac; int dp_norm_valid;
     // exposures (st3r_ctx_set_exposure, gs_exposure.hip)
     ViewReg ex; const float* ex_exposure; float* ex_v_exposure;
+    // intrinsics gradient (st3r_ctx_set_intrinsics_grad, gs_intrinsics.hip): where d loss / d (fx, fy, cx, cy) goes
+    ViewReg kg; float* kg_v_Ks;
     int bwd_stamp;  // generation stamp of the per-(record, tile) partial-gradient slots
     int depth_stamp;  // the same for the depth backward's slots (SLOT_VTILE_DEPTH)
     uint32_t scan_gen;   // single-pass scan (gs_isect.hip): generation of its status words

@@ -385,8 +385,11 @@ static int train_views(st3r_ctx* ctx, hipStream_t s, const GsParams& g, const Vi
     StepImages im;
     rc = step_images(ctx, ro, need_pairs, ex.exposure != nullptr, &im);
     if (rc) return rc;
+    // an intrinsics gradient registered for these views (st3r_ctx_set_intrinsics_grad): it needs the per-pair array as
+    // the pose gradient does
+    float* const v_Ks = st3r_intrinsics_grad_for(ctx, b.gt, v.C, v.H, v.W);
     float* v_pairs = nullptr;   // per-pair gradients [N*C, 12]: the projection backward's input and / or the pose backward's
-    if (need_pairs || b.v_viewmats) {
+    if (need_pairs || b.v_viewmats || v_Ks) {
         ARENA_GET(SLOT_VSPLATS, float, ro.n_pairs * ST3R_SPLAT_STRIDE, vp);
         v_pairs = vp;
     }
@@ -405,10 +408,15 @@ static int train_views(st3r_ctx* ctx, hipStream_t s, const GsParams& g, const Vi
     st3r_prof_end(ctx, s, STG_PROJECT_BWD);
     // poses without a depth prior, two launches BEHIND the ones of a call without poses: k_gather_vtile materialises the
     // per-pair sums of the slots (the projection backward above summed the same slots itself and is left as it is)
-    if (!rc && !need_pairs && b.v_viewmats) {
+    if (!rc && !need_pairs && (b.v_viewmats || v_Ks)) {
         rc = st3r_gather_vtile_impl(s, ro.n_pairs, &slots, v_pairs);
-        if (!rc) rc = pose_backward(ctx, s, g, v, ro, v_pairs, b.v_viewmats);
+        if (!rc && b.v_viewmats) rc = pose_backward(ctx, s, g, v, ro, v_pairs, b.v_viewmats);
     }
+    // the stand-alone intrinsics backward on the same per-pair gradients (with a depth prior: the summed ones), behind
+    // everything a call without the registration launches
+    if (!rc && v_Ks)
+        rc = st3r_gs_intrinsics_bwd(ctx, s, g.N, v.C, g.means, g.quats, g.scales, v.viewmats, v.Ks, v.W, v.H, 0.3f,
+                                    ro.splats, v_pairs, v_Ks);
     return rc;
 }
 
@@ -476,6 +484,12 @@ int st3r_train_fwd_bwd_impl(st3r_ctx* ctx, hipStream_t s, const GsParams& g, con
     if (ex.exposure && ctx->comm) {
         st3r_set_error("exposures are registered and a communicator is attached -- per-view exposures are not supported "
                        "in view-sharded training (clear them with st3r_ctx_set_exposure(ctx, NULL, ...))");
+        return ST3R_ERR_INVALID;
+    }
+    // an intrinsics gradient registered for these views (st3r_ctx_set_intrinsics_grad): the same rule
+    if (ctx->comm && st3r_intrinsics_grad_for(ctx, gt_images, C, v.H, v.W)) {
+        st3r_set_error("an intrinsics gradient is registered and a communicator is attached -- intrinsics refinement is "
+                       "not supported in view-sharded training (clear it with st3r_ctx_set_intrinsics_grad(ctx, NULL, ...))");
         return ST3R_ERR_INVALID;
     }
     st3r_prof_next_step(ctx);

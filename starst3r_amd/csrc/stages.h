@@ -126,6 +126,10 @@ int st3r_exposure_fwd_impl(hipStream_t s, int C, int H, int W, const float* rgb,
 int st3r_exposure_bwd_impl(st3r_ctx* ctx, hipStream_t s, int C, int H, int W, const float* rgb, const float* exposure,
                            const float* v_out, float* v_rgb, float* v_exposure);
 
+// ---- gs_intrinsics.hip ----
+// the rows of the registered intrinsics gradient [C,4] of the C views at `gt`; NULL: none applies
+float* st3r_intrinsics_grad_for(st3r_ctx* ctx, const float* gt, int C, int H, int W);
+
 // ---- adam.hip ----
 // i0 < 0: the whole buffer.  [g0, g1) a proper sub-range of the Gaussians: that range instead of [i0, i1).
 int st3r_adam_impl(hipStream_t s, int N, float* means, float* quats, float* scales, float* opacities, float* sh,

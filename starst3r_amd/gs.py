@@ -193,17 +193,18 @@ RENDER_MODES = ("RGB", "D", "ED", "RGB+D", "RGB+ED")   # gsplat.rasterization's 
 
 
 class _Rasterize(torch.autograd.Function):
-    """Differentiable wrapper so user code can still back-propagate through render_3dgs: into the Gaussians and, when
-    w2c requires a gradient, into the camera poses.  want_depth: returns (rgb, alpha, depth) -- the depth map of the same
+    """Differentiable wrapper so user code can still back-propagate through render_3dgs: into the Gaussians, when
+    w2c requires a gradient into the camera poses, and with want_Ks into the intrinsics (st3r_gs_intrinsics_bwd).
+    want_depth: returns (rgb, alpha, depth) -- the depth map of the same
     render (st3r_gs_blend_depth_fwd) -- and back-propagates from any of them; without it (rgb, alpha), and no depth
     kernel runs, forward or backward.  The per-pair gradients of the colour and of the depth backward are summed and go
     through project_sh_bwd / viewmat_bwd once; the depth column (z of the record) is added by st3r_gs_depth_bwd."""
 
     @staticmethod
-    def forward(fctx, means, quats, scales, opacities, shN, w2c, Ks, width, height, ctx, want_depth):
+    def forward(fctx, means, quats, scales, opacities, shN, w2c, Ks, width, height, ctx, want_depth, want_Ks=False):
         rgb, alpha, info = ops.rasterization(ctx, means, quats, scales, opacities, shN, w2c, Ks, width, height)
         fctx.save_for_backward(means, quats, scales, opacities, shN, w2c, Ks, alpha)
-        fctx.info, fctx.ctx, fctx.wh = info, ctx, (width, height)
+        fctx.info, fctx.ctx, fctx.wh, fctx.want_Ks = info, ctx, (width, height), want_Ks
         if not want_depth:
             return rgb, alpha
         fctx.set_materialize_grads(False)   # an output the loss does not use costs no backward kernel
@@ -233,17 +234,22 @@ class _Rasterize(torch.autograd.Function):
             v_splats = torch.zeros_like(info["_splats"])
         grads = ops.project_sh_bwd(ctx, means, quats, scales, opacities, shN, w2c, Ks, info["_campos"], W, H,
                                    info["_splats"], v_splats)
-        # camera poses: only when asked for (gsplat's v_viewmats); intrinsics get none, as in gsplat
-        v_w2c = None
+        # camera poses: only when asked for (gsplat's v_viewmats); intrinsics: only with scene.intrinsics_grad
+        # (gsplat returns none) -- the depth column of v_splats does not depend on K
+        v_w2c = v_Ks = None
         if fctx.needs_input_grad[5]:
             v_w2c = ops.viewmat_bwd(ctx, means, quats, scales, shN, w2c, Ks, info["_campos"], W, H, info["_splats"],
                                     v_splats)
+        if fctx.want_Ks and fctx.needs_input_grad[6]:
+            v4 = ops.intrinsics_bwd(ctx, means, quats, scales, w2c, Ks, W, H, info["_splats"], v_splats)
+            v_Ks = torch.zeros_like(Ks)
+            v_Ks[:, 0, 0] = v4[:, 0]; v_Ks[:, 1, 1] = v4[:, 1]; v_Ks[:, 0, 2] = v4[:, 2]; v_Ks[:, 1, 2] = v4[:, 3]
         if v_depth is not None:
             ops.depth_bwd(ctx, means, w2c, info["_splats"], v_splats, grads, v_w2c)
         G = ops.split_grads(grads, N)
         v_sh = torch.zeros_like(shN)
         v_sh[:, :4] = G["sh"]
-        return G["means"], G["quats"], G["scales"], G["opacities"], v_sh, v_w2c, None, None, None, None, None
+        return G["means"], G["quats"], G["scales"], G["opacities"], v_sh, v_w2c, v_Ks, None, None, None, None, None
 
 
 class _Exposure(torch.autograd.Function):
@@ -281,7 +287,11 @@ def render_3dgs(scene, w2c: torch.Tensor, intrinsics: torch.Tensor, width: int, 
     (expected depth D / clamp(alpha, min=1e-10)) return render_img (N,H,W,1); "RGB+D" and "RGB+ED" return (N,H,W,4)
     with the depth last.  Every mode back-propagates into the Gaussians and, when it requires a gradient, into w2c.
     exposure (not in the reference): a (N,3,4) tensor, one affine colour transform [A | t] per view, applied to the RGB
-    channels of render_img (y = A x + t); differentiable into the Gaussians, w2c and exposure."""
+    channels of render_img (y = A x + t); differentiable into the Gaussians, w2c and exposure.
+    scene.intrinsics_grad (not in the reference; gsplat returns no such gradient; a setting of the scene, default False,
+    because the argument list above is the boundary users program against): True makes the backward pass return
+    d loss / d intrinsics as well when `intrinsics` requires a gradient -- (N,3,3), non-zero at fx, fy, cx, cy -- in every
+    render_mode; with False no kernel for it runs and intrinsics.grad stays None."""
     if render_mode not in RENDER_MODES:
         raise ValueError(f"render_mode must be one of {RENDER_MODES}, got {render_mode!r}")
     if exposure is not None:
@@ -292,7 +302,7 @@ def render_3dgs(scene, w2c: torch.Tensor, intrinsics: torch.Tensor, width: int, 
     if exposure is not None:
         exposure = exposure.to(scene.device, torch.float32)
     out = _Rasterize.apply(g["means"], g["quats"], g["scales"], g["opacities"], g["shN"], w2c, Ks, width, height, ctx,
-                           render_mode != "RGB")
+                           render_mode != "RGB", bool(getattr(scene, "intrinsics_grad", False)))
     if render_mode == "RGB":
         rgb, alpha = out
         img = rgb if exposure is None else _Exposure.apply(rgb, exposure, ctx)
@@ -368,14 +378,19 @@ def _depth_prior_on_device(scene, views, conf_thres, height, width):
     return scene._depth_dev[1], scene._depth_dev[2]
 
 
-def _exposure_frozen(n_views, exposure_freeze):
-    """sorted view indices of exposure_freeze (negative ones count from the end); ValueError outside [-n_views, n_views)"""
+def _view_indices(n_views, freeze, option):
+    """sorted view indices of the option `freeze` (negative ones count from the end); ValueError outside [-n_views, n_views)"""
     out = set()
-    for i in exposure_freeze:
+    for i in freeze:
         if isinstance(i, bool) or int(i) != i or not -n_views <= int(i) < n_views:
-            raise ValueError(f"exposure_freeze holds {i!r}: not the index of one of the {n_views} views")
+            raise ValueError(f"{option} holds {i!r}: not the index of one of the {n_views} views")
         out.add(int(i) % n_views)
     return sorted(out)
+
+
+def _exposure_frozen(n_views, exposure_freeze):
+    """_view_indices of exposure_freeze"""
+    return _view_indices(n_views, exposure_freeze, "exposure_freeze")
 
 
 def _on(value, schedule=False):
@@ -458,6 +473,20 @@ def run_3dgs_optim(
     gauge between colours and exposures.  render_3dgs_original(exposure=True) renders through them.  Works together with
     pose_lr, depth_fac and enable_pruning; single process, Gaussians replicated only.  With exposure_lr == 0 nothing about
     the call changes and scene.exposures is not created.
+
+    scene.intrinsics_lr, scene.intrinsics_freeze, scene.intrinsics_tie_focal, scene.intrinsics_opt_pp (not in the reference;
+    settings of the scene, defaults 0.0, (), True, False, because the argument list above is the boundary users program
+    against and stays as it is).  intrinsics_lr is a float or a callable step -> float as pose_lr: when not 0.0 the views'
+    intrinsics are refined inside the same fused step -- the focal the alignment estimated is off by a few per cent for
+    few views, and no pose update removes that.  Adam (the Gaussians' betas and eps) on (log fx, log fy, cx / W, cy / H) of
+    every view, so one rate serves every image size.  intrinsics_tie_focal (default): one focal scalar per view, fx / fy
+    keeps its value; intrinsics_opt_pp: the principal point is trained too (default: it stays).  The views in
+    intrinsics_freeze keep their row bit for bit.  The loop trains a private float32 copy; when it ends scene.intrinsics
+    is REPLACED by a new tensor of its old dtype and device.  Moments and step counter persist on scene._gs_optim (k_m,
+    k_v, k_step).  Focal length and camera distance are nearly degenerate for a single view: the intended use is together
+    with pose_lr and with at least one frozen view, so that the other views' geometry decides between the two.  Works
+    together with pose_lr, depth_fac, exposure_lr and enable_pruning; single process, Gaussians replicated only.  With
+    intrinsics_lr == 0 nothing about the call changes and scene.intrinsics is not touched.
     """
     poses_on, depth_on = _on(pose_lr, schedule=True), _on(depth_fac)
     if depth_on:
@@ -468,6 +497,14 @@ def run_3dgs_optim(
     if exposure_on:   # (checked before anything runs)
         _single_replica_only("exposure_lr", scene, enable_pruning)
         exp_frozen = _exposure_frozen(len(scene.imgs), exposure_freeze)
+    intrinsics_lr = getattr(scene, "intrinsics_lr", 0.0)
+    intrinsics_freeze = getattr(scene, "intrinsics_freeze", ())
+    intrinsics_tie_focal = getattr(scene, "intrinsics_tie_focal", True)
+    intrinsics_opt_pp = getattr(scene, "intrinsics_opt_pp", False)
+    intrinsics_on = _on(intrinsics_lr, schedule=True)
+    if intrinsics_on:   # (checked before anything runs)
+        _single_replica_only("scene.intrinsics_lr", scene, enable_pruning)
+        k_frozen = _view_indices(len(scene.imgs), intrinsics_freeze, "scene.intrinsics_freeze")
     height, width = scene.imgs[0].shape[:2]
     ctx = ops.get_context(scene.device)
     st = scene._gs_optim
@@ -505,6 +542,12 @@ def run_3dgs_optim(
         _per_view_moments(st, "exp", 12 * n_img, gt.device)
         st.exp_grad = torch.zeros((n_img, 3, 4), device=gt.device)   # this step's d loss / d exposures (diagnostics)
         exp_mask = _freeze_mask(n_img, exp_frozen, gt.device)
+    if intrinsics_on:
+        Ks = Ks.clone()   # a private copy, trained in place; scene.intrinsics follows when the loop ends
+        n_k = Ks.shape[0]
+        _per_view_moments(st, "k", 4 * n_k, Ks.device)   # (new when the views changed)
+        st.k_grad = torch.zeros((n_k, 4), device=Ks.device)   # this step's d loss / d (fx, fy, cx, cy) (diagnostics)
+        k_mask = _freeze_mask(n_k, k_frozen, Ks.device)
     restore_exchange = None
     if enable_pruning and fused and world > 1 and ops.get_exchange(ctx) in ("rs_ag", "direct"):
         # reduce-scatter exchange (through RCCL or through the peers' exported buffers): a rank maintains the Adam moments of its piece of the buffer only; growing the set
@@ -550,6 +593,10 @@ def run_3dgs_optim(
         if exposure_on:   # behind the step on the same stream, and behind the same device-side guard as its updates
             ops.exposure_adam_step(ctx, scene.exposures, st.exp_grad, st.exp_m, st.exp_v, _rate_at(exposure_lr, step),
                                    st.betas[0], st.betas[1], st.eps, st.exp_step, exp_mask)
+        if intrinsics_on:   # the same: behind the step, which wrote st.k_grad at the intrinsics it started with
+            ops.intrinsics_adam_step(ctx, Ks, st.k_grad, st.k_m, st.k_v, _rate_at(intrinsics_lr, step), st.betas[0],
+                                     st.betas[1], st.eps, st.k_step, k_mask, width, height, bool(intrinsics_tie_focal),
+                                     bool(intrinsics_opt_pp))
 
     def capacity_error(e):
         return getattr(e, "code", 0) == -3 and world == 1
@@ -560,6 +607,8 @@ def run_3dgs_optim(
             st.pose_step += d
         if exposure_on:
             st.exp_step += d
+        if intrinsics_on:
+            st.k_step += d
 
     # A peer failure (ST3R_ERR_PEER: the step before failed on some rank, nobody applied it) ABORTS the run on every rank
     # alike -- all ranks get the code from the same call --; the exchange form is restored whatever ends the loop.
@@ -572,6 +621,8 @@ def run_3dgs_optim(
             ops.set_depth_prior(ctx, gt, prior, prior_w, float(depth_fac))
         if exposure_on:   # and so do the exposures
             ops.set_exposure(ctx, gt, scene.exposures, st.exp_grad)
+        if intrinsics_on:
+            ops.set_intrinsics_grad(ctx, gt, st.k_grad)
         step = 0
         for _ in it_range:
             if enable_pruning:
@@ -622,6 +673,8 @@ def run_3dgs_optim(
             ops.set_depth_prior(ctx, None, None, None)
         if exposure_on:
             ops.set_exposure(ctx, None, None, None)
+        if intrinsics_on:
+            ops.set_intrinsics_grad(ctx, None, None)
         if sh_c[0].shape[0] == g["shN"].shape[0]:
             sh_write_back()
         if restore_exchange is not None:   # (the moments stay complete on every rank: rs_ag goes on using its own piece)
@@ -633,6 +686,13 @@ def run_3dgs_optim(
             if frozen:
                 c2w[frozen] = old.detach()[frozen]
             scene.c2w = c2w
+        if intrinsics_on:
+            # a NEW intrinsics tensor, device and dtype as before; frozen views keep their rows bit for bit
+            old = scene.intrinsics
+            K_new = Ks.to(device=old.device, dtype=old.dtype)
+            if k_frozen:
+                K_new[k_frozen] = old.detach()[k_frozen]
+            scene.intrinsics = K_new
     _dist.all_reduce_sum(losses)
     return losses[:iters].cpu().tolist()   # one device->host copy for the whole call (reference: .item() per step)
 

@@ -272,6 +272,17 @@ def viewmat_bwd(ctx, means, quats, scales, sh, viewmats, Ks, campos, W, H, splat
     return v_viewmats
 
 
+def intrinsics_bwd(ctx, means, quats, scales, viewmats, Ks, W, H, splats, v_splats, eps2d=0.3, out=None):
+    """d loss / d (fx, fy, cx, cy) [C,4] from the per-pair gradients of blend_bwd, the clamp limits' dependence on K
+    included (st3r_gs_intrinsics_bwd)."""
+    N, Cn = means.shape[0], viewmats.shape[0]
+    v_Ks = out if out is not None else torch.empty((Cn, 4), dtype=torch.float32, device=means.device)
+    _lib.check(_lib.lib().st3r_gs_intrinsics_bwd(
+        ctx.handle, _stream(), N, Cn, _p(means), _p(quats), _p(scales), _p(viewmats), _p(Ks), W, H, eps2d, _p(splats),
+        _p(v_splats), _p(v_Ks)))
+    return v_Ks
+
+
 def split_grads(grads, N):
     """views into the block layout means[3N] quats[4N] scales[3N] opacities[N] sh4[12N]"""
     return dict(means=grads[0:3 * N].view(N, 3), quats=grads[3 * N:7 * N].view(N, 4),
@@ -370,6 +381,26 @@ def set_exposure(ctx, gt, exposure, v_exposure):
     The caller's tensors are kept alive here."""
     _set_registration(ctx, "exposure", "_ex_keep", gt, (exposure, v_exposure),
                       lambda: tuple(exposure.shape) == (gt.shape[0], 3, 4) and v_exposure.shape == exposure.shape)
+
+
+def intrinsics_adam_step(ctx, Ks, v_Ks, k_m, k_v, lr, b1, b2, eps, step, mask, W, H, tie_focal=True, opt_pp=False):
+    """One Adam step on the intrinsics Ks [C,3,3], in place, from v_Ks [C,4] = d loss / d (fx, fy, cx, cy); moments
+    k_m / k_v [4C]; the parameters are (log fx, log fy, cx / W, cy / H) (st3r_intrinsics_adam_step).  tie_focal: one
+    focal scalar per view (moment slot 0; fx / fy is kept); opt_pp: the principal point is trained too.  mask [C] floats
+    or None: views with mask == 0 keep every bit."""
+    Cn = Ks.shape[0]
+    assert tuple(Ks.shape) == (Cn, 3, 3) and v_Ks.numel() == 4 * Cn and k_m.numel() == 4 * Cn and k_v.numel() == 4 * Cn
+    _lib.check(_lib.lib().st3r_intrinsics_adam_step(ctx.handle, _stream(), Cn, _p(Ks), _p(v_Ks), _p(k_m), _p(k_v), lr, b1,
+                                                    b2, eps, step, _p(mask), W, H,
+                                                    (1 if tie_focal else 0) | (2 if opt_pp else 0)))
+
+
+def set_intrinsics_grad(ctx, gt, v_Ks):
+    """Register the buffer v_Ks [C,4] that receives d loss / d (fx, fy, cx, cy) of the images gt [C,H,W,3] --
+    train_fwd_bwd, train_step and train_step_poses on `gt` (or whole views of it) then write it
+    (st3r_ctx_set_intrinsics_grad) -- or clear the registration (gt = None).  The caller's tensors are kept alive here."""
+    _set_registration(ctx, "intrinsics_grad", "_kg_keep", gt, (v_Ks,),
+                      lambda: v_Ks.is_contiguous() and tuple(v_Ks.shape) == (gt.shape[0], 4))
 
 
 def adam_step(ctx, params, grads, m, v, lr, b1, b2, eps, step):

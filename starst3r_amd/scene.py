@@ -30,6 +30,16 @@ class Scene:
         self.depth_confs = []
         self.c2w = None
         self.intrinsics = None
+        # not in the reference: refinement of `intrinsics` (gs.py).  Settings of the scene, not arguments: the argument
+        # lists of run_3dgs_optim and render_3dgs are the boundary users program against and stay as they are.
+        # intrinsics_lr (a float or a callable step -> float; 0.0: off), intrinsics_freeze (view indices),
+        # intrinsics_tie_focal, intrinsics_opt_pp: read by run_3dgs_optim; intrinsics_grad: render_3dgs also
+        # back-propagates into an `intrinsics` argument that requires a gradient
+        self.intrinsics_lr = 0.0
+        self.intrinsics_freeze = ()
+        self.intrinsics_tie_focal = True
+        self.intrinsics_opt_pp = False
+        self.intrinsics_grad = False
         self.optim_params = None
         # declared by the reference but never written (scene.py:42-45,74-77); the names in use are the ones
         # init_3dgs sets: gaussians, optimizers, ssim, strategy, strategy_state (gs.py:20,37,39,43,45)
