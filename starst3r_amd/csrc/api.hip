@@ -95,6 +95,8 @@ int st3r_arena_get2(st3r_ctx* ctx, int slot, size_t bytes, void** out, int* grow
 // which: 0 = sorted pair ids ("flatten ids", int32 [n_isects]), 1 = tile offsets (int32 [C*tiles]),
 //        2 = splat records (float [C*N*12]), 3 = inclusive tile scan in pair-id order (int32 [C*N])
 //        11 / 12 = emitted tile keys / pair ids (the tile sort's input), 13 = sorted tile keys (uint32 / int32 [n_isects])
+//        Packed tile sort (banded form, N * C <= 2^24, debug flag 1024 clear): 11 and 13 stay allocated but are NOT written
+//        (whatever an earlier step left), 12 = the packed words pair id | low key byte << 24, 0 = clean pair ids.
 ST3R_EXPORT int st3r_ctx_peek(st3r_ctx* ctx, void* stream, int which, void* dst, int64_t bytes) {
     ARG_CHECK(ctx && dst && bytes >= 0 && which >= 0 && which <= 13);
     static const int slots[14] = {SLOT_VALS_B, SLOT_OFFSETS, SLOT_SPLATS, SLOT_CUM,

@@ -149,7 +149,9 @@ struct st3r_ctx {
     int debug_flags;  // st3r_ctx_set_debug: bit 0 = blend forward ignores the per-quadrant relevance test; 1: backward
                       // recomputes the tile rectangles; 2 (4): level-1 sort on (camera | depth) keys in four passes; 3: async capacity halved; 4 (16): plain emission and two-pass tile sort instead of the banded form; 8 (256, acts when set): the scans' status-word generations jump to two or three launches before their wrap; 5: training calls start at 2 view chunks;
                       // 6: backward gathers rectangle and slot base separately; 7 (128): training forward on the quadrant
-                      // kernel; 9 (512): st3r_gs_render on the cell-list kernel; 11 (2048): under a communicator
+                      // kernel; 9 (512): st3r_gs_render on the cell-list kernel; 10 (1024): the banded tile sort keeps its
+                      // two arrays (tile keys next to pair ids, offsets read from the sorted keys) instead of the packed
+                      // word (fused_step.hip: rasterize_front); 11 (2048): under a communicator
                       // st3r_gs_train_step behaves as if this rank's forward / backward had failed (comm.hip)
                       // (round 5's experiment switches -- 4096 masked rectangles, 8192 cell-granular backward, 16384 slot sums
                       // in a kernel of their own -- left the library in round 6: tools/experiments/README.md)

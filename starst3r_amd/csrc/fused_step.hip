@@ -178,27 +178,38 @@ static int rasterize_front(st3r_ctx* ctx, hipStream_t s, const GsParams& g, cons
     ARENA_GET(SLOT_VALS_B, int32_t, n_isects, vals_b);
     // the sort and the offsets read the record count from device memory in both paths: the pair-order scan's total
     o->n_records = async ? -1 : n_isects;
+    const int64_t n_keys = (int64_t)C * tile_w * tile_h;
+    const uint32_t* band_table = nullptr;
+    const uint32_t* band_hist = nullptr;   // packed tile sort: the records of every (band, low key byte)
+    int n_bands = 0;
     if (n_isects > 0) {
         // Keys of 9 .. 16 bits: the emission writes the records split by the high byte of their key (the "band"), in
         // (camera, depth) order inside every band, and ONE stable pass on the low byte inside every band is left of the
         // tile sort -- the same (camera, tile, depth) order as the two passes (debug flag 16), bit for bit.
         const int end_bit = fp.end_bit;
         const bool banded = st3r_sort_tile_banded(end_bit, ctx->debug_flags) != 0;
-        const int n_bands = (int)(((int64_t)C * tile_w * tile_h - 1) >> 8) + 1;
-        const uint32_t* band_table = nullptr;
+        // Packed form of the banded sort (pair ids below 2^24; debug flag 1024 keeps the two arrays): behind the banded
+        // emission a record's position fixes its band, the high key byte, so the emission writes ONE word per record,
+        // pair id | low key byte << 24, into vals_a, the pass sorts that word keys-only and stores the bare pair ids, and
+        // the offsets come from the band table and the band histograms.  tkeys_a / tkeys_b are not written.
+        const bool packed = banded && n_pairs <= (1 << 24) && !(ctx->debug_flags & 1024);
+        n_bands = (int)((n_keys - 1) >> 8) + 1;
         st3r_prof_begin(ctx, s, STG_EMIT);
-        rc = st3r_isect_emit_chain_impl(ctx, s, N, C, perm, rects, rect32, tile_w, tile_h, tkeys_a, vals_a, n_isects,
-                                        banded ? st3r_sort_tile_banded_tile(n_isects) : 0, total_dev, &band_table);
+        rc = st3r_isect_emit_chain_impl(ctx, s, N, C, perm, rects, rect32, tile_w, tile_h, packed ? nullptr : tkeys_a, vals_a,
+                                        n_isects, banded ? st3r_sort_tile_banded_tile(n_isects) : 0, total_dev, &band_table);
         st3r_prof_end(ctx, s, STG_EMIT);
         if (rc) return rc;
         st3r_prof_begin(ctx, s, STG_SORT);
-        rc = banded ? st3r_sort_tile_banded_impl(ctx, s, n_isects, n_bands, band_table, tkeys_a, vals_a, tkeys_b, vals_b)
-                    : st3r_sort_tile_impl(ctx, s, n_isects, end_bit, tkeys_a, vals_a, tkeys_b, vals_b, total_dev);
+        rc = packed ? st3r_radix_sort_u32_banded_packed(ctx, s, n_isects, n_bands, band_table, (const uint32_t*)vals_a, vals_b,
+                                                        &band_hist)
+             : banded ? st3r_sort_tile_banded_impl(ctx, s, n_isects, n_bands, band_table, tkeys_a, vals_a, tkeys_b, vals_b)
+                      : st3r_sort_tile_impl(ctx, s, n_isects, end_bit, tkeys_a, vals_a, tkeys_b, vals_b, total_dev);
         st3r_prof_end(ctx, s, STG_SORT);
         if (rc) return rc;
     }
     st3r_prof_begin(ctx, s, STG_OFFSETS);
-    rc = st3r_isect_offsets32_impl(s, n_isects, tkeys_b, C, tile_w, tile_h, offsets, total_dev);
+    rc = band_hist ? st3r_radix_band_offsets(s, n_bands, band_table, band_hist, n_keys, offsets)
+                   : st3r_isect_offsets32_impl(s, n_isects, tkeys_b, C, tile_w, tile_h, offsets, total_dev);
     st3r_prof_end(ctx, s, STG_OFFSETS);
     if (rc) return rc;
     o->C = C; o->W = W; o->H = H; o->tile_w = tile_w; o->tile_h = tile_h;

@@ -756,6 +756,9 @@ __global__ __launch_bounds__(256) void k_isect_emit_d(int N, int C, int bpc, con
 //                    the chunk is regrouped by band in LDS and leaves in runs that are contiguous in the destination
 //                    (stored straight from the ranking lanes a wave's 64 outputs meet ~20 of the 33 bands of a 1080p
 //                    camera, a dozen bytes per run: that form took twice the time of the plain emission).
+//                    tile_keys == NULL: the packed form, one word per record, pair id | low key byte << 24, in vals -- a
+//                    record's position fixes its band, the high key byte, so only the low byte is information (pair ids
+//                    below 2^24; radix_sort.hip: PACKED).
 // A camera owns the bands first_band(c) = (c n_tiles) >> 8 .. ((c + 1) n_tiles - 1) >> 8; neighbouring cameras share a
 // band when n_tiles is no multiple of 256.  Counter of (camera c, local band j, workgroup k): cam_off(c) + j bpc + k with
 // cam_off(c) = bpc * (bands of the cameras in front) -- band-major, and camera-major inside a shared band.
@@ -941,8 +944,12 @@ __global__ __launch_bounds__(256) void k_isect_emit_b(int N, int C, int bpc, con
             const uint32_t v = s_srt[i], band = (v >> 8) & 0xFFu;
             const uint32_t pos = s_pos[band] + (uint32_t)i;
             if ((int64_t)pos < cap) {
-                tile_keys[pos] = (((uint32_t)bl.first + band) << 8) | (v & 0xFFu);
-                vals[pos] = s_pid[v >> 16];
+                if (tile_keys) {
+                    tile_keys[pos] = (((uint32_t)bl.first + band) << 8) | (v & 0xFFu);
+                    vals[pos] = s_pid[v >> 16];
+                } else {   // packed: the position fixes the band, the low key byte rides above the pair id (< 2^24)
+                    vals[pos] = (int32_t)((uint32_t)s_pid[v >> 16] | (v << 24));
+                }
             }
         }
         __syncthreads();
@@ -993,7 +1000,8 @@ void st3r_isect_constants(int64_t out[5]) {
 }
 
 // band_tile > 0: the banded emission for a sort tile of that many items; *band_table then receives the table of
-// k_band_table (device memory, valid until the next call), n_dev is the record count on the device
+// k_band_table (device memory, valid until the next call), n_dev is the record count on the device; tile_keys == NULL then
+// asks for the packed form (N * C <= 2^24): vals receives pair id | low key byte << 24 and no key is written
 int st3r_isect_emit_chain_impl(st3r_ctx* ctx, hipStream_t s, int N, int C, const int32_t* perm, const void* rects,
                                int rect32, int tile_w, int tile_h, uint32_t* tile_keys, int32_t* vals, int64_t cap,
                                int band_tile, const int32_t* n_dev, const uint32_t** band_table) {

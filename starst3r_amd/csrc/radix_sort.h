@@ -29,3 +29,11 @@ void st3r_radix_sort_shape(int key_bytes, int64_t n, int64_t seg_n, int n_seg, i
 int st3r_radix_sort_band_tile(int64_t n_cap);
 int st3r_radix_sort_u32_banded(st3r_ctx* ctx, hipStream_t s, int64_t n_cap, int n_bands, const uint32_t* band_table,
                                const uint32_t* keys_in, const int32_t* vals_in, uint32_t* keys_out, int32_t* vals_out);
+// The same pass on ONE word per record, pair id | low key byte << 24 (pair ids below 2^24): ids_out receives the pair ids
+// in sorted order, no keys leave.  *band_hist (device, valid until the next sort of this ctx): the records of every
+// (band, low byte), from which st3r_radix_band_offsets writes offsets[k] = first sorted position of key k for k < total and
+// offsets[total] = the record count -- before or after the pass, bands without a record included.
+int st3r_radix_sort_u32_banded_packed(st3r_ctx* ctx, hipStream_t s, int64_t n_cap, int n_bands, const uint32_t* band_table,
+                                      const uint32_t* words_in, int32_t* ids_out, const uint32_t** band_hist);
+int st3r_radix_band_offsets(hipStream_t s, int n_bands, const uint32_t* band_table, const uint32_t* band_hist, int64_t total,
+                            int32_t* offsets);

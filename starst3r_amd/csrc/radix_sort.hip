@@ -18,7 +18,9 @@
 //                    and leave in runs that are contiguous in the destination.
 //   k_rs_hist_band / k_rs_pass<.., BAND>   the level-2 sort behind the banded emission (gs_isect.hip): the stream is already
 //                    split by the high key byte, one stable low-byte pass inside every band is all that is left.
-// Traffic per pass: one read and one write of keys and values (+ 2 KB of status words per tile).
+//   k_rs_pass<.., BAND, PACKED> / k_band_offsets   the same pass on one word per record (pair id | low key byte << 24): the
+//                    pair ids leave bare, no key does, and the tile offsets come from the band starts and histograms.
+// Traffic per pass: one read and one write of keys and values (+ 2 KB of status words per tile); packed: of one word.
 #include "radix_sort.h"
 
 namespace {
@@ -166,8 +168,11 @@ __global__ __launch_bounds__(HIST_THREADS) void k_rs_hist_seg(const uint32_t* __
 // table travels through LDS), the chained scan restarts at the band's first tile, hist_base + 256 band is the band's own
 // low-byte histogram, and one pass on bits [0, 8) writes the caller's output.  The grid is sized for the capacity
 // (n / TILE + n_bands tiles); tickets past the tiles in use return at once.
+// PACKED (with BAND): the stream is ONE word per record, pair id | low key byte << 24 (k_isect_emit_b's packed form) -- the
+// pass runs keys-only on that word at shift 24 and its store phase writes word & 0x00FFFFFF, the pair id, to vout.  No key
+// output (the offsets come from the band histograms: k_band_offsets), no value array in LDS, no value registers.
 constexpr int BAND_TAB = ST3R_BAND_TAB;
-template <typename K, int THREADS, int IPT, bool SEG = false, bool BAND = false>
+template <typename K, int THREADS, int IPT, bool SEG = false, bool BAND = false, bool PACKED = false>
 __global__ __launch_bounds__(THREADS) void k_rs_pass(const K* __restrict__ kin, const int32_t* __restrict__ vin,
                                                      K* __restrict__ kout, int32_t* __restrict__ vout, int64_t n,
                                                      int shift, int bits, const uint32_t* __restrict__ hist_base,
@@ -178,6 +183,7 @@ __global__ __launch_bounds__(THREADS) void k_rs_pass(const K* __restrict__ kin, 
                                                      int32_t* __restrict__ vtmp = nullptr,
                                                      const uint32_t* __restrict__ band_tab = nullptr, int n_bands = 0) {
     static_assert(!(SEG && BAND), "one kind of segment per launch");
+    static_assert(!PACKED || (BAND && sizeof(K) == 4), "the packed word is the banded tile sort's");
     if (n_dev) n = min(n, (int64_t)max(*n_dev, 0));   // count on the device, grid sized for the capacity `n`
     constexpr int TILE = THREADS * IPT, WAVES = THREADS / 64;
     uint32_t kmin = 0, ktop = 0;
@@ -196,7 +202,7 @@ __global__ __launch_bounds__(THREADS) void k_rs_pass(const K* __restrict__ kin, 
         shift = RB * ps; bits = RB;
     }
     __shared__ K sbuf[TILE];
-    __shared__ int32_t svals[TILE];   // values regroup together with the keys: one trip through LDS, one store phase
+    __shared__ int32_t svals[PACKED ? 1 : TILE];   // values regroup together with the keys: one trip through LDS, one store phase
     __shared__ uint32_t whist[WAVES][RADIX];
     __shared__ uint32_t lbase[RADIX];
     __shared__ uint32_t tcnt[RADIX];
@@ -267,11 +273,11 @@ __global__ __launch_bounds__(THREADS) void k_rs_pass(const K* __restrict__ kin, 
     }
     // SEG, pass 0: the values ARE the item indices (pair ids) -- nothing is read, and the projection does not write them
     const bool iota_vals = SEG && ps == 0;
-    const bool has_vals = SEG || vin != nullptr;
+    const bool has_vals = !PACKED && (SEG || vin != nullptr);
     if (iota_vals) {
 #pragma unroll
         for (int i = 0; i < IPT; ++i) val[i] = (int32_t)(tbase + wbase + i * 64);
-    } else if (vin) {   // in flight while the keys are ranked
+    } else if (has_vals) {   // in flight while the keys are ranked
 #pragma unroll
         for (int i = 0; i < IPT; ++i) {
             const int li = wbase + i * 64;
@@ -388,8 +394,12 @@ __global__ __launch_bounds__(THREADS) void k_rs_pass(const K* __restrict__ kin, 
             const K k = sbuf[p];
             const uint32_t d = (uint32_t)(k >> shift) & dmask;
             const long long o = gofs[d] + p;
-            if (!(SEG && last_seg_pass)) kout[o] = k;   // (nobody reads the level-1 keys once the pairs are in order)
-            if (has_vals) vout[o] = svals[p];
+            if constexpr (PACKED) {
+                vout[o] = (int32_t)((uint32_t)k & 0x00FFFFFFu);   // (nobody reads the tile keys either: k_band_offsets)
+            } else {
+                if (!(SEG && last_seg_pass)) kout[o] = k;   // (nobody reads the level-1 keys once the pairs are in order)
+                if (has_vals) vout[o] = svals[p];
+            }
         }
     }
 }
@@ -516,10 +526,11 @@ int sort_pairs_seg(st3r_ctx* ctx, hipStream_t s, int64_t seg_n, int n_seg, const
 
 // Low-byte histogram of every band of a banded stream: workgroup g owns the contiguous range [g per, (g + 1) per) of the
 // stream (not a grid stride), walks the bands that meet it -- one or two when the bands are longer than a range -- and
-// flushes 256 counters per band it saw.  hist: [n_bands][256].
+// flushes 256 counters per band it saw.  hist: [n_bands][256].  shift: where the low key byte sits in a word of the stream
+// (0: tile keys, 24: packed words).
 __global__ __launch_bounds__(HIST_THREADS) void k_rs_hist_band(const uint32_t* __restrict__ keys, int64_t per,
                                                                const uint32_t* __restrict__ band_tab, int n_bands,
-                                                               uint32_t* __restrict__ hist) {
+                                                               uint32_t* __restrict__ hist, int shift) {
     __shared__ uint32_t sh[HIST_THREADS / 64][RADIX];
     __shared__ uint32_t s_start[BAND_TAB];
     for (int i = threadIdx.x; i <= n_bands; i += HIST_THREADS) s_start[i] = band_tab[i];
@@ -548,7 +559,7 @@ __global__ __launch_bounds__(HIST_THREADS) void k_rs_hist_band(const uint32_t* _
             }
 #pragma unroll
             for (int i = 0; i < HIST_ITEMS; ++i)
-                if (base + i * HIST_THREADS + threadIdx.x < a1) atomicAdd(&mine[k[i] & (RADIX - 1)], 1u);
+                if (base + i * HIST_THREADS + threadIdx.x < a1) atomicAdd(&mine[(k[i] >> shift) & (RADIX - 1)], 1u);
         }
         __syncthreads();
         for (int i = threadIdx.x; i < RADIX; i += HIST_THREADS) {
@@ -561,8 +572,32 @@ __global__ __launch_bounds__(HIST_THREADS) void k_rs_hist_band(const uint32_t* _
     }
 }
 
+// Tile offsets of the packed banded sort, from what is known before the pass runs: offsets[b 256 + d] = start of band b +
+// the records of the band whose low key byte is below d -- the first sorted position of (camera, tile) key b 256 + d.  One
+// workgroup per band, empty bands included (they have no sort tile, so the pass could not write their entries);
+// offsets[total] = the record count as k_band_table clamped it.
+__global__ __launch_bounds__(RADIX) void k_band_offsets(const uint32_t* __restrict__ band_tab, int n_bands,
+                                                        const uint32_t* __restrict__ hist, int64_t total,
+                                                        int32_t* __restrict__ offsets) {
+    __shared__ uint32_t s_wsum[RADIX / 64];
+    const int b = blockIdx.x, d = threadIdx.x, lane = d & 63, w = d >> 6;
+    const uint32_t h = hist[(size_t)b * RADIX + d];
+    const uint32_t inc = wave_incl_scan_u32(h, lane);
+    if (lane == 63) s_wsum[w] = inc;
+    __syncthreads();
+    uint32_t excl = inc - h;
+#pragma unroll
+    for (int i = 0; i < RADIX / 64; ++i) excl += i < w ? s_wsum[i] : 0u;
+    const int64_t key = (int64_t)b * RADIX + d;
+    if (key < total) offsets[key] = (int32_t)(band_tab[b] + excl);
+    if (b == n_bands - 1 && d == 0) offsets[total] = (int32_t)band_tab[n_bands];
+}
+
+// packed_hist != NULL: the packed form (see k_rs_pass) -- keys_in holds the packed words, vals_in and keys_out are not
+// used, vals_out receives the pair ids, and *packed_hist the band histograms for st3r_radix_band_offsets (valid until the
+// next sort of this ctx)
 int sort_pairs_banded(st3r_ctx* ctx, hipStream_t s, int64_t n, int n_bands, const uint32_t* band_tab, const uint32_t* keys_in,
-                      const int32_t* vals_in, uint32_t* keys_out, int32_t* vals_out) {
+                      const int32_t* vals_in, uint32_t* keys_out, int32_t* vals_out, const uint32_t** packed_hist = nullptr) {
     if (n == 0) return ST3R_OK;
     typedef uint32_t K;
     if (n_bands < 1 || n_bands > BAND_TAB - 1) { st3r_set_error("banded radix sort: 1 .. 256 bands"); return ST3R_ERR_INVALID; }
@@ -581,15 +616,22 @@ int sort_pairs_banded(st3r_ctx* ctx, hipStream_t s, int64_t n, int n_bands, cons
     // after the other: 72 us at 26 M keys)
     const int hist_blocks = (int)std::min<int64_t>(2048, (n + CH - 1) / CH);
     const int64_t per = ((n + hist_blocks - 1) / hist_blocks + CH - 1) / CH * CH;
-    hipLaunchKernelGGL(k_rs_hist_band, dim3(hist_blocks), dim3(HIST_THREADS), 0, s, keys_in, per, band_tab, n_bands, hist);
-    if (sh.small)
-        hipLaunchKernelGGL((k_rs_pass<K, THREADS_S, Traits<K>::IPT_S, false, true>), dim3((unsigned)ntiles), dim3(THREADS_S), 0, s,
-                           keys_in, vals_in, keys_out, vals_out, n, 0, RB, hist, status, counters, (const int32_t*)nullptr,
-                           (int64_t)0, 0, (const uint32_t*)nullptr, 0, (K*)nullptr, (int32_t*)nullptr, band_tab, n_bands);
-    else
-        hipLaunchKernelGGL((k_rs_pass<K, THREADS_L, Traits<K>::IPT, false, true>), dim3((unsigned)ntiles), dim3(THREADS_L), 0, s,
-                           keys_in, vals_in, keys_out, vals_out, n, 0, RB, hist, status, counters, (const int32_t*)nullptr,
-                           (int64_t)0, 0, (const uint32_t*)nullptr, 0, (K*)nullptr, (int32_t*)nullptr, band_tab, n_bands);
+    const bool packed = packed_hist != nullptr;
+    hipLaunchKernelGGL(k_rs_hist_band, dim3(hist_blocks), dim3(HIST_THREADS), 0, s, keys_in, per, band_tab, n_bands, hist,
+                       packed ? 24 : 0);
+    // (one argument list for the four instantiations; packed: shift 24, no value input, no key output)
+#define RS_BAND_PASS(THREADS, IPT, PACKED)                                                                                    \
+    hipLaunchKernelGGL((k_rs_pass<K, THREADS, IPT, false, true, PACKED>), dim3((unsigned)ntiles), dim3(THREADS), 0, s, keys_in,   \
+                       PACKED ? (const int32_t*)nullptr : vals_in, PACKED ? (K*)nullptr : keys_out, vals_out, n,              \
+                       PACKED ? 24 : 0, RB, hist, status, counters, (const int32_t*)nullptr, (int64_t)0, 0,                   \
+                       (const uint32_t*)nullptr, 0, (K*)nullptr, (int32_t*)nullptr, band_tab, n_bands)
+    if (packed) {
+        if (sh.small) RS_BAND_PASS(THREADS_S, Traits<K>::IPT_S, true); else RS_BAND_PASS(THREADS_L, Traits<K>::IPT, true);
+        *packed_hist = hist;
+    } else {
+        if (sh.small) RS_BAND_PASS(THREADS_S, Traits<K>::IPT_S, false); else RS_BAND_PASS(THREADS_L, Traits<K>::IPT, false);
+    }
+#undef RS_BAND_PASS
     LAUNCH_CHECK();
     return ST3R_OK;
 }
@@ -601,6 +643,19 @@ int st3r_radix_sort_band_tile(int64_t n_cap) { return (int)band_shape(n_cap).til
 int st3r_radix_sort_u32_banded(st3r_ctx* ctx, hipStream_t s, int64_t n_cap, int n_bands, const uint32_t* band_table,
                                const uint32_t* keys_in, const int32_t* vals_in, uint32_t* keys_out, int32_t* vals_out) {
     return sort_pairs_banded(ctx, s, n_cap, n_bands, band_table, keys_in, vals_in, keys_out, vals_out);
+}
+
+int st3r_radix_sort_u32_banded_packed(st3r_ctx* ctx, hipStream_t s, int64_t n_cap, int n_bands, const uint32_t* band_table,
+                                      const uint32_t* words_in, int32_t* ids_out, const uint32_t** band_hist) {
+    *band_hist = nullptr;
+    return sort_pairs_banded(ctx, s, n_cap, n_bands, band_table, words_in, nullptr, nullptr, ids_out, band_hist);
+}
+
+int st3r_radix_band_offsets(hipStream_t s, int n_bands, const uint32_t* band_table, const uint32_t* band_hist, int64_t total,
+                            int32_t* offsets) {
+    hipLaunchKernelGGL(k_band_offsets, dim3(n_bands), dim3(RADIX), 0, s, band_table, n_bands, band_hist, total, offsets);
+    LAUNCH_CHECK();
+    return ST3R_OK;
 }
 
 void st3r_radix_sort_shape(int key_bytes, int64_t n, int64_t seg_n, int n_seg, int begin_bit, int end_bit, int64_t out[8]) {

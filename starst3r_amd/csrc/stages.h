@@ -75,7 +75,8 @@ int st3r_scan_tiles(int64_t n);
 void st3r_emit_grid(int N, int C, int* bpc, int* grid, int* self_base);
 void st3r_isect_constants(int64_t out[5]);
 // band_tile > 0: the banded emission (records split by the high byte of their key) and, in *band_table, the band starts and
-// sort tiles for st3r_sort_tile_banded_impl: two arrays of ST3R_BAND_TAB words (gs_isect.hip: k_band_table)
+// sort tiles for st3r_sort_tile_banded_impl: two arrays of ST3R_BAND_TAB words (gs_isect.hip: k_band_table); tile_keys == NULL
+// (banded only, N * C <= 2^24): the packed form, vals = pair id | low key byte << 24 (st3r_radix_sort_u32_banded_packed)
 int st3r_isect_emit_chain_impl(st3r_ctx* ctx, hipStream_t s, int N, int C, const int32_t* perm, const void* rects,
                                int rect32, int tile_w, int tile_h, uint32_t* tile_keys, int32_t* vals, int64_t cap,
                                int band_tile, const int32_t* n_dev, const uint32_t** band_table);
