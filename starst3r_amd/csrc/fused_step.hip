@@ -6,8 +6,6 @@
 #include "radix_sort.h"
 #include "stages.h"
 
-static int bit_length_u32(uint32_t v) { int n = 0; while (v) { ++n; v >>= 1; } return n; }
-
 // The previous asynchronous step left its record count in pinned memory behind an event: pick it up (it completed long
 // ago), remember it as the sizing hint, and fail loudly if that step ran out of capacity (its records past the
 // capacity were dropped, so its gradients were incomplete).
@@ -124,7 +122,7 @@ static int rasterize_front(st3r_ctx* ctx, hipStream_t s, const GsParams& g, cons
     // (segments: the keys WITHOUT the camera bits, one segment of N pairs per camera, biased and sorted in as many 8-bit
     // passes as the depth range of the call needs -- radix_sort.hip: SEG)
     rc = krange ? st3r_radix_sort_u32_segments(ctx, s, N, C, (uint32_t*)dkeys_a, dvals_a, (uint32_t*)dkeys_b, perm, krange)
-         : key32 ? st3r_radix_sort_u32(ctx, s, n_pairs, 0, fp.l1_end_bit, (uint32_t*)dkeys_a, dvals_a, (uint32_t*)dkeys_b, perm)
+         : key32 ? st3r_radix_sort_u32(ctx, s, n_pairs, 0, fp.l1_end_bit, (uint32_t*)dkeys_a, dvals_a, (uint32_t*)dkeys_b, perm, nullptr)
                  : st3r_radix_sort_u64(ctx, s, n_pairs, 0, fp.l1_end_bit, dkeys_a, dvals_a, dkeys_b, perm);
     st3r_prof_end(ctx, s, STG_SORT_DEPTH);
     if (rc) return rc;
@@ -196,13 +194,13 @@ static int rasterize_front(st3r_ctx* ctx, hipStream_t s, const GsParams& g, cons
         n_bands = (int)((n_keys - 1) >> 8) + 1;
         st3r_prof_begin(ctx, s, STG_EMIT);
         rc = st3r_isect_emit_chain_impl(ctx, s, N, C, perm, rects, rect32, tile_w, tile_h, packed ? nullptr : tkeys_a, vals_a,
-                                        n_isects, banded ? st3r_sort_tile_banded_tile(n_isects) : 0, total_dev, &band_table);
+                                        n_isects, banded ? st3r_radix_sort_band_tile(n_isects) : 0, total_dev, &band_table);
         st3r_prof_end(ctx, s, STG_EMIT);
         if (rc) return rc;
         st3r_prof_begin(ctx, s, STG_SORT);
         rc = packed ? st3r_radix_sort_u32_banded_packed(ctx, s, n_isects, n_bands, band_table, (const uint32_t*)vals_a, vals_b,
                                                         &band_hist)
-             : banded ? st3r_sort_tile_banded_impl(ctx, s, n_isects, n_bands, band_table, tkeys_a, vals_a, tkeys_b, vals_b)
+             : banded ? st3r_radix_sort_u32_banded(ctx, s, n_isects, n_bands, band_table, tkeys_a, vals_a, tkeys_b, vals_b)
                       : st3r_sort_tile_impl(ctx, s, n_isects, end_bit, tkeys_a, vals_a, tkeys_b, vals_b, total_dev);
         st3r_prof_end(ctx, s, STG_SORT);
         if (rc) return rc;
@@ -634,7 +632,7 @@ ST3R_EXPORT int st3r_front_plan(int N, int C, int width, int height, int debug_f
     if (st3r_sort_tile_banded(fp.end_bit, debug_flags)) {
         out[18] = 1;
         out[19] = (((int64_t)C * fp.tile_w * fp.tile_h - 1) >> 8) + 1;
-        if (n_records > 0) out[30] = n_records / st3r_sort_tile_banded_tile(n_records) + out[19];
+        if (n_records > 0) out[30] = n_records / st3r_radix_sort_band_tile(n_records) + out[19];
     }
     int64_t k[5];
     st3r_isect_constants(k);

@@ -9,36 +9,11 @@
 // All integer work: results are bit-exact against oracle/gs_oracle.c.
 #include "stages.h"
 #include "tile_rect.h"
+#include "wave_prims.h"
 
 #define SCAN_THREADS 256
 #define SCAN_ITEMS 16
 #define SCAN_TILE (SCAN_THREADS * SCAN_ITEMS)
-
-__device__ __forceinline__ int wave_incl_scan(int v) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        int t = __shfl_up(v, off);
-        if (lane >= off) v += t;
-    }
-    return v;
-}
-
-// block-wide inclusive scan of one int per thread (256 threads = 4 waves); returns inclusive value,
-// *total receives the block total
-__device__ __forceinline__ int block_incl_scan(int v, int* total) {
-    __shared__ int wsum[4];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int inc = wave_incl_scan(v);
-    if (lane == 63) wsum[w] = inc;
-    __syncthreads();
-    int base = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) base += (i < w) ? wsum[i] : 0;
-    *total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-    __syncthreads();
-    return inc + base;
-}
 
 // Single-pass prefix sum (decoupled look-back, Merrill & Garland 2016, restated for wave64): a workgroup owns a tile of
 // 4096 consecutive elements, publishes the tile's sum as soon as it is known, and adds up the published sums of its
@@ -298,8 +273,6 @@ __global__ __launch_bounds__(256) void k_isect_emit(int N, int64_t n_pairs, cons
         }
 }
 
-static int bit_length_u32(uint32_t v) { int n = 0; while (v) { ++n; v >>= 1; } return n; }
-
 static int st3r_isect_emit_impl(hipStream_t s, int N, int C, const float* splats, const int32_t* cum, int tile_size,
                                 int tile_w, int tile_h, int64_t* isect_ids, int32_t* flatten_ids) {
     int64_t n_pairs = (int64_t)N * C;
@@ -549,16 +522,8 @@ __global__ __launch_bounds__(256) void k_isect_gather(int N, int C, int bpc, con
     for (int j = 0; j < EPT; ++j) {
         if (pid[j] >= 0) {
             const int64_t dst = first + j * 256 + t;
-            uint32_t org, rw, rh;   // origin x0 | y0 << 16, width, height: rect_load's decode of either form
-            if (rect32) {
-                const uint32_t r = reinterpret_cast<const uint32_t*>(rects)[pid[j]];
-                reinterpret_cast<uint32_t*>(rects_d)[dst] = r;
-                org = (r & 0xFFu) | ((r & 0xFF00u) << 8); rw = (r >> 16) & 0xFFu; rh = r >> 24;
-            } else {
-                const uint64_t r = reinterpret_cast<const uint64_t*>(rects)[pid[j]];
-                reinterpret_cast<uint64_t*>(rects_d)[dst] = r;
-                org = (uint32_t)(r & 0xFFFFFFFFull); rw = (uint32_t)((r >> 32) & 0xFFFF); rh = (uint32_t)(r >> 48);
-            }
+            uint32_t org, rw, rh;   // origin x0 | y0 << 16, width, height; the packed word itself moves into depth order
+            rect_load<true>(rects, rect32, pid[j], &org, &rw, &rh, rects_d, dst);
             sum += (int)rw * (int)rh;
             if (bcnt && rw)
                 for (uint32_t ty = 0; ty < rh; ++ty) {
@@ -593,12 +558,7 @@ __global__ __launch_bounds__(1024) void k_isect_wg_scan(int n, const int32_t* __
     const int e0 = min(t * per, n), e1 = min(e0 + per, n);
     long long sum = 0;
     for (int e = e0; e < e1; ++e) sum += wg_tiles[e];
-    long long inc = sum;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const long long o = __shfl_up(inc, off);
-        if (lane >= off) inc += o;
-    }
+    const long long inc = wave_incl_scan(sum);
     if (lane == 63) s_wave[w] = inc;
     __syncthreads();
     long long base = 0;
@@ -608,19 +568,139 @@ __global__ __launch_bounds__(1024) void k_isect_wg_scan(int n, const int32_t* __
     for (int e = e0; e < e1; ++e) { wg_base[e] = run; run += wg_tiles[e]; }
 }
 
+// ---- the pair walk shared by the two emission kernels below (k_isect_emit_d, k_isect_emit_b) ----
+// The LDS of the walk (the kernels declare the arrays and size `own` for their chunk):
+struct EmitLds {
+    int* end;         // [EP] inclusive scan of the workgroup's tile counts
+    uint32_t* org;    // [EP] x0 | y0 << 16
+    uint16_t* w;      // [EP] rectangle width (< 2^16 in both packed forms)
+    int32_t* pid;     // [EP]
+    uint16_t* own;    // [chunk] owner (pair index + 1) of every output of the current emission chunk
+    unsigned* wmax;   // [4]
+};
+
+// the workgroup's np pairs (depth order, from `first`) into LDS and the scan of their tile counts; returns the workgroup's total
+__device__ __forceinline__ int emit_load_pairs(const int32_t* __restrict__ perm, const void* __restrict__ rects_d, int rect32,
+                                               int64_t first, int np, const EmitLds& L) {
+    const int t = threadIdx.x;
+    int cnt[EPT];
+#pragma unroll
+    for (int j = 0; j < EPT; ++j) {
+        const int e = j * 256 + t;
+        int32_t pid = 0;
+        uint32_t org = 0, rw = 0, rh = 0;
+        if (e < np) {
+            pid = perm[first + e];
+            rect_load(rects_d, rect32, first + e, &org, &rw, &rh);
+        }
+        L.pid[e] = pid; L.org[e] = org; L.w[e] = (uint16_t)rw;
+        cnt[j] = (int)(rw * rh);
+    }
+    // scan in pair order: EPT block scans of 256 consecutive pairs, the carry in a register
+    int carry = 0;
+#pragma unroll
+    for (int j = 0; j < EPT; ++j) {
+        int tot;
+        const int inc = block_incl_scan(cnt[j], &tot);
+        L.end[j * 256 + t] = carry + inc;
+        carry += tot;
+    }
+    __syncthreads();
+    return carry;
+}
+
+// The owners of the CH outputs [c0, c0 + CH) of the workgroup into L.own: every pair with tiles marks its first output with
+// its index + 1, a prefix maximum spreads the marks to the right -- thread t scans its CH / 256 consecutive entries in
+// registers, the thread maxima meet in a wave scan and the four wave maxima in L.wmax.  *carry_owner (uniform): owner (+1) of
+// the last output of the previous chunk, for a chunk whose first outputs hold no mark.  Three barriers; a caller may clear
+// LDS of its own right before the call, in the barrier interval of the clearing of L.own.
+template <int CH>
+__device__ __forceinline__ void emit_owners(int c0, int np, const EmitLds& L, int* carry_owner) {
+    // thread t owns NW 32-bit words (two owners each) of L.own, moved VW words at a time: 128-bit LDS accesses at CH = 4096
+    constexpr int NW = CH / 512, VW = NW % 4 == 0 ? 4 : 1, NV = NW / VW;
+    typedef unsigned Vec __attribute__((ext_vector_type(VW)));
+    Vec* const own = reinterpret_cast<Vec*>(L.own);
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+#pragma unroll
+    for (int q = 0; q < NV; ++q) own[t + 256 * q] = Vec{};
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < EPT; ++j) {
+        const int e = j * 256 + t;
+        if (e < np) {
+            const int start = e ? L.end[e - 1] : 0;
+            if (L.end[e] > start && start >= c0 && start < c0 + CH) L.own[start - c0] = (uint16_t)(e + 1);
+        }
+    }
+    __syncthreads();
+    unsigned wv[NW];
+#pragma unroll
+    for (int q = 0; q < NV; ++q) {
+        const Vec v = own[NV * t + q];
+#pragma unroll
+        for (int i = 0; i < VW; ++i) wv[q * VW + i] = v[i];
+    }
+    unsigned run = 0;   // running maximum over this thread's entries
+#pragma unroll
+    for (int i = 0; i < NW; ++i) {
+        const unsigned lo = max(run, wv[i] & 0xFFFFu);
+        run = max(lo, wv[i] >> 16);
+        wv[i] = lo | (run << 16);
+    }
+    const unsigned inc = wave_incl_scan<WaveMax>(run);   // inclusive prefix maximum over the wave
+    if (lane == 63) L.wmax[w] = inc;
+    const unsigned excl_m = wave_prev(inc, 0u);
+    __syncthreads();
+    unsigned pre = max((unsigned)*carry_owner, excl_m);
+#pragma unroll
+    for (int ww = 0; ww < 4; ++ww)
+        if (ww < w) pre = max(pre, L.wmax[ww]);
+    *carry_owner = (int)max(max(max((unsigned)*carry_owner, L.wmax[0]), max(L.wmax[1], L.wmax[2])), L.wmax[3]);
+#pragma unroll
+    for (int i = 0; i < NW; ++i) {
+        const unsigned lo = max(wv[i] & 0xFFFFu, pre), hi = max(wv[i] >> 16, pre);
+        wv[i] = lo | (hi << 16);
+    }
+#pragma unroll
+    for (int q = 0; q < NV; ++q) {
+        Vec v;
+#pragma unroll
+        for (int i = 0; i < VW; ++i) v[i] = wv[q * VW + i];
+        own[NV * t + q] = v;
+    }
+    __syncthreads();
+}
+
+// Output i of the chunk at c0: its owner *p (index among the workgroup's pairs) and the key of its tile, key0 being the
+// camera's first key
+__device__ __forceinline__ uint32_t emit_decode(int i, int c0, uint32_t key0, int tile_w, const EmitLds& L, int* p_out) {
+    const int p = (int)L.own[i] - 1;
+    const int kk = c0 + i - (p == 0 ? 0 : L.end[p - 1]);   // index among the pair's emitted tiles, row major
+    const uint32_t w_ = L.w[p], org = L.org[p];
+    // kk / w with kk < w * h <= 2^20 and w < 2^10: float estimate, corrected by one either way
+    int qq = (int)((float)kk * __builtin_amdgcn_rcpf((float)w_));
+    int rem = kk - qq * (int)w_;
+    if (rem < 0) { --qq; rem += (int)w_; }
+    if (rem >= (int)w_) { ++qq; rem -= (int)w_; }
+    *p_out = p;
+    const uint32_t tx = (org & 0xFFFF) + (uint32_t)rem, ty = (org >> 16) + (uint32_t)qq;
+    return key0 + ty * (uint32_t)tile_w + tx;
+}
+
 __global__ __launch_bounds__(256) void k_isect_emit_d(int N, int C, int bpc, const int32_t* __restrict__ perm,
                                                       const void* __restrict__ rects_d, int rect32,
                                                       const long long* __restrict__ wg_base,
                                                       const int32_t* __restrict__ wg_tiles, int tile_w, int tile_h,
                                                       uint32_t* __restrict__ tile_keys, int32_t* __restrict__ vals,
                                                       int64_t cap) {
-    __shared__ int s_end[EP];         // inclusive scan of the workgroup's tile counts
-    __shared__ uint32_t s_org[EP];    // x0 | y0 << 16
-    __shared__ uint16_t s_w[EP];      // rectangle width (< 2^16 in both packed forms; 22.6 KB of LDS in all: seven workgroups per CU)
+    __shared__ int s_end[EP];
+    __shared__ uint32_t s_org[EP];
+    __shared__ uint16_t s_w[EP];      // (22.6 KB of LDS in all: seven workgroups per CU)
     __shared__ int32_t s_pid[EP];
-    __shared__ uint16_t s_own[ECH];   // owner (pair index + 1) of every output of the current emission chunk
+    __shared__ uint16_t s_own[ECH];
     __shared__ unsigned s_wmax[4];
     __shared__ long long s_bsum[4];
+    const EmitLds L = {s_end, s_org, s_w, s_pid, s_own, s_wmax};
     int c, k;
     emit_item(C, bpc, &c, &k);
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
@@ -637,30 +717,7 @@ __global__ __launch_bounds__(256) void k_isect_emit_d(int N, int C, int bpc, con
     }
     const int64_t first = (int64_t)c * N + (int64_t)k * EP;
     const int np = (int)min((int64_t)EP, (int64_t)(c + 1) * N - first);
-    int cnt[EPT];
-#pragma unroll
-    for (int j = 0; j < EPT; ++j) {
-        const int e = j * 256 + t;
-        int32_t pid = 0;
-        uint32_t org = 0, rw = 0, rh = 0;
-        if (e < np) {
-            pid = perm[first + e];
-            rect_load(rects_d, rect32, first + e, &org, &rw, &rh);
-        }
-        s_pid[e] = pid; s_org[e] = org; s_w[e] = (uint16_t)rw;
-        cnt[j] = (int)(rw * rh);
-    }
-    // scan in pair order: EPT block scans of 256 consecutive pairs, the carry in a register
-    int carry = 0;
-#pragma unroll
-    for (int j = 0; j < EPT; ++j) {
-        int tot;
-        const int inc = block_incl_scan(cnt[j], &tot);
-        s_end[j * 256 + t] = carry + inc;
-        carry += tot;
-    }
-    const int total = carry;
-    __syncthreads();
+    const int total = emit_load_pairs(perm, rects_d, rect32, first, np, L);
     // (a true count above 2^31 wraps the int32 pair-order scan: the position test below keeps such writes out)
     long long base;
     if (wg_base) base = wg_base[c * bpc + k];
@@ -674,65 +731,14 @@ __global__ __launch_bounds__(256) void k_isect_emit_d(int N, int C, int bpc, con
     const uint32_t key0 = (uint32_t)c * (uint32_t)(tile_w * tile_h);
     int carry_owner = 0;   // owner (+1) of the last output of the previous chunk (uniform)
     for (int c0 = 0; c0 < total; c0 += ECH) {
-        reinterpret_cast<uint4*>(s_own)[t] = make_uint4(0u, 0u, 0u, 0u);
-        reinterpret_cast<uint4*>(s_own)[t + 256] = make_uint4(0u, 0u, 0u, 0u);
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < EPT; ++j) {
-            const int e = j * 256 + t;
-            if (e < np) {
-                const int start = e ? s_end[e - 1] : 0;
-                if (s_end[e] > start && start >= c0 && start < c0 + ECH) s_own[start - c0] = (uint16_t)(e + 1);
-            }
-        }
-        __syncthreads();
-        uint4 a = reinterpret_cast<const uint4*>(s_own)[2 * t], b = reinterpret_cast<const uint4*>(s_own)[2 * t + 1];
-        unsigned wv[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-        unsigned run = 0;   // running maximum over this thread's 16 entries
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const unsigned lo = max(run, wv[i] & 0xFFFFu);
-            run = max(lo, wv[i] >> 16);
-            wv[i] = lo | (run << 16);
-        }
-        unsigned inc = run;   // inclusive prefix maximum over the wave
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const unsigned o = __shfl_up(inc, off);
-            if (lane >= off) inc = max(inc, o);
-        }
-        if (lane == 63) s_wmax[w] = inc;
-        unsigned excl_m = __shfl_up(inc, 1);
-        if (lane == 0) excl_m = 0;
-        __syncthreads();
-        unsigned pre = max((unsigned)carry_owner, excl_m);
-#pragma unroll
-        for (int ww = 0; ww < 4; ++ww)
-            if (ww < w) pre = max(pre, s_wmax[ww]);
-        carry_owner = (int)max(max(max((unsigned)carry_owner, s_wmax[0]), max(s_wmax[1], s_wmax[2])), s_wmax[3]);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const unsigned lo = max(wv[i] & 0xFFFFu, pre), hi = max(wv[i] >> 16, pre);
-            wv[i] = lo | (hi << 16);
-        }
-        reinterpret_cast<uint4*>(s_own)[2 * t] = make_uint4(wv[0], wv[1], wv[2], wv[3]);
-        reinterpret_cast<uint4*>(s_own)[2 * t + 1] = make_uint4(wv[4], wv[5], wv[6], wv[7]);
-        __syncthreads();
+        emit_owners<ECH>(c0, np, L, &carry_owner);
         const int lim = min(ECH, total - c0);
         for (int i = t; i < lim; i += 256) {
-            const int p = (int)s_own[i] - 1;
-            const int o = c0 + i;
-            const int kk = o - (p == 0 ? 0 : s_end[p - 1]);   // index among the pair's emitted tiles, row major
-            const uint32_t w_ = s_w[p], org = s_org[p];
-            // kk / w with kk < w * h <= 2^20 and w < 2^10: float estimate, corrected by one either way
-            int qq = (int)((float)kk * __builtin_amdgcn_rcpf((float)w_));
-            int rem = kk - qq * (int)w_;
-            if (rem < 0) { --qq; rem += (int)w_; }
-            if (rem >= (int)w_) { ++qq; rem -= (int)w_; }
-            const uint32_t tx = (org & 0xFFFF) + (uint32_t)rem, ty = (org >> 16) + (uint32_t)qq;
-            const long long pos = base + o;
+            int p;
+            const uint32_t key = emit_decode(i, c0, key0, tile_w, L, &p);
+            const long long pos = base + (c0 + i);
             if (pos >= 0 && pos < cap) {
-                tile_keys[pos] = key0 + ty * (uint32_t)tile_w + tx;
+                tile_keys[pos] = key;
                 vals[pos] = s_pid[p];
             }
         }
@@ -749,7 +755,7 @@ __global__ __launch_bounds__(256) void k_isect_emit_d(int N, int C, int bpc, con
 //                    keys [key0 + ty tile_w + x0, + w), w < 256, which meet at most two bands;
 //   (one chained scan over the counters, band-major and then in workgroup order c * bpc + k -- see band_layout)
 //   k_band_table     band starts and lengths, the sort tiles of every band, the tiles in use;
-//   k_isect_emit_b   k_isect_emit_d's decode; inside a chunk a wave owns ECH_B / 4 consecutive outputs (rows of 64), lanes
+//   k_isect_emit_b   k_isect_emit_d's pair walk (emit_load_pairs, emit_owners, emit_decode); inside a chunk a wave owns ECH_B / 4 consecutive outputs (rows of 64), lanes
 //                    of a row that share a band find each other with ballots (as many as the camera's band count needs
 //                    bits: 6 at 8 x 1080p), per-wave band counters in LDS, after the chunk's barrier an exclusive prefix
 //                    over the four waves and a running count per band across the chunks (a register of thread `band`);
@@ -773,7 +779,7 @@ __global__ __launch_bounds__(256) void k_isect_emit_b(int N, int C, int bpc, con
                                                       const int32_t* __restrict__ binc, int tile_w, int tile_h, int bits,
                                                       uint32_t* __restrict__ tile_keys, int32_t* __restrict__ vals,
                                                       int64_t cap) {
-    constexpr int ROWS = ECH_B / 256, NWV = ECH_B / 512;   // rows of 64 outputs per wave; 32-bit words of s_own per thread
+    constexpr int ROWS = ECH_B / 256;   // rows of 64 outputs per wave
     __shared__ int s_end[EP];
     __shared__ uint32_t s_org[EP];
     __shared__ uint16_t s_w[EP];
@@ -781,6 +787,7 @@ __global__ __launch_bounds__(256) void k_isect_emit_b(int N, int C, int bpc, con
     __shared__ uint16_t s_own[ECH_B];
     __shared__ uint32_t s_srt[ECH_B];   // the chunk regrouped by band: pair index << 16 | local band << 8 | low key byte
     __shared__ unsigned s_wmax[4];
+    const EmitLds L = {s_end, s_org, s_w, s_pid, s_own, s_wmax};
     // per band of the camera (sized at the launch, 16 bytes a band): the chunk's first position minus its first regrouped
     // index, that index, and the four waves' counters (uint16)
     extern __shared__ uint32_t s_band[];
@@ -794,29 +801,7 @@ __global__ __launch_bounds__(256) void k_isect_emit_b(int N, int C, int bpc, con
     uint16_t* s_bc = reinterpret_cast<uint16_t*>(s_band + 2 * nbl);   // [4][nbl]
     const int64_t first = (int64_t)c * N + (int64_t)k * EP;
     const int np = (int)min((int64_t)EP, (int64_t)(c + 1) * N - first);
-    int cnt[EPT];
-#pragma unroll
-    for (int j = 0; j < EPT; ++j) {
-        const int e = j * 256 + t;
-        int32_t pid = 0;
-        uint32_t org = 0, rw = 0, rh = 0;
-        if (e < np) {
-            pid = perm[first + e];
-            rect_load(rects_d, rect32, first + e, &org, &rw, &rh);
-        }
-        s_pid[e] = pid; s_org[e] = org; s_w[e] = (uint16_t)rw;
-        cnt[j] = (int)(rw * rh);
-    }
-    int carry = 0;
-#pragma unroll
-    for (int j = 0; j < EPT; ++j) {
-        int tot;
-        const int inc = block_incl_scan(cnt[j], &tot);
-        s_end[j * 256 + t] = carry + inc;
-        carry += tot;
-    }
-    const int total = carry;
-    __syncthreads();
+    const int total = emit_load_pairs(perm, rects_d, rect32, first, np, L);
     // thread b < nbl keeps the next free position of band b of this workgroup (nbl <= 256: keys of at most 16 bits)
     uint32_t run = 0;
     if (t < nbl) {
@@ -828,53 +813,8 @@ __global__ __launch_bounds__(256) void k_isect_emit_b(int N, int C, int bpc, con
     uint16_t* bc = s_bc + w * nbl;
     int carry_owner = 0;
     for (int c0 = 0; c0 < total; c0 += ECH_B) {
-#pragma unroll
-        for (int q = 0; q < NWV; ++q) reinterpret_cast<uint32_t*>(s_own)[t + 256 * q] = 0u;
-        for (int b = lane; b < nbl; b += 64) bc[b] = 0;
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < EPT; ++j) {
-            const int e = j * 256 + t;
-            if (e < np) {
-                const int start = e ? s_end[e - 1] : 0;
-                if (s_end[e] > start && start >= c0 && start < c0 + ECH_B) s_own[start - c0] = (uint16_t)(e + 1);
-            }
-        }
-        __syncthreads();
-        // prefix maximum of the marks, as in k_isect_emit_d: thread t owns 2 NWV consecutive entries
-        unsigned wv[NWV];
-#pragma unroll
-        for (int q = 0; q < NWV; ++q) wv[q] = reinterpret_cast<const uint32_t*>(s_own)[NWV * t + q];
-        unsigned runm = 0;
-#pragma unroll
-        for (int i = 0; i < NWV; ++i) {
-            const unsigned lo = max(runm, wv[i] & 0xFFFFu);
-            runm = max(lo, wv[i] >> 16);
-            wv[i] = lo | (runm << 16);
-        }
-        unsigned inc = runm;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const unsigned o = __shfl_up(inc, off);
-            if (lane >= off) inc = max(inc, o);
-        }
-        if (lane == 63) s_wmax[w] = inc;
-        unsigned excl_m = __shfl_up(inc, 1);
-        if (lane == 0) excl_m = 0;
-        __syncthreads();
-        unsigned pre = max((unsigned)carry_owner, excl_m);
-#pragma unroll
-        for (int ww = 0; ww < 4; ++ww)
-            if (ww < w) pre = max(pre, s_wmax[ww]);
-        carry_owner = (int)max(max(max((unsigned)carry_owner, s_wmax[0]), max(s_wmax[1], s_wmax[2])), s_wmax[3]);
-#pragma unroll
-        for (int i = 0; i < NWV; ++i) {
-            const unsigned lo = max(wv[i] & 0xFFFFu, pre), hi = max(wv[i] >> 16, pre);
-            wv[i] = lo | (hi << 16);
-        }
-#pragma unroll
-        for (int q = 0; q < NWV; ++q) reinterpret_cast<uint32_t*>(s_own)[NWV * t + q] = wv[q];
-        __syncthreads();
+        for (int b = lane; b < nbl; b += 64) bc[b] = 0;   // (cleared in emit_owners' first barrier interval)
+        emit_owners<ECH_B>(c0, np, L, &carry_owner);
         const int lim = min(ECH_B, total - c0);
         // rank: wave w owns the outputs [w ECH_B / 4, (w + 1) ECH_B / 4) of the chunk, row by row;
         // item = local band << 24 | low key byte << 16 | rank among the wave's records of that band in this chunk
@@ -885,23 +825,11 @@ __global__ __launch_bounds__(256) void k_isect_emit_b(int N, int C, int bpc, con
             const bool valid = i < lim;
             uint32_t key = 0, band = 0;
             if (valid) {
-                const int p = (int)s_own[i] - 1;
-                const int kk = c0 + i - (p == 0 ? 0 : s_end[p - 1]);
-                const uint32_t w_ = s_w[p], org = s_org[p];
-                // kk / w with kk < w * h <= 2^20 and w < 2^10: float estimate, corrected by one either way
-                int qq = (int)((float)kk * __builtin_amdgcn_rcpf((float)w_));
-                int rem = kk - qq * (int)w_;
-                if (rem < 0) { --qq; rem += (int)w_; }
-                if (rem >= (int)w_) { ++qq; rem -= (int)w_; }
-                key = key0 + ((org >> 16) + (uint32_t)qq) * (uint32_t)tile_w + (org & 0xFFFF) + (uint32_t)rem;
+                int p;
+                key = emit_decode(i, c0, key0, tile_w, L, &p);
                 band = (key >> 8) - (uint32_t)bl.first;
             }
-            u64 m = __ballot(valid);
-            for (int bb = 0; bb < bits; ++bb) {
-                const bool bit = (band >> bb) & 1u;
-                const u64 bal = __ballot(bit);
-                m &= bit ? bal : ~bal;
-            }
+            WAVE_MATCH(m, valid, band, bits)
             const uint32_t below = (uint32_t)__popcll(m & lt);
             uint32_t prev = 0;
             if (valid) {

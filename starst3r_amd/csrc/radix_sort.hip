@@ -9,7 +9,7 @@
 //   k_rs_pass        one launch per 8-bit digit.  A workgroup (16 waves; 8 for small inputs) owns a tile of 16384 (32-bit keys) or 8192
 //                    (64-bit keys) consecutive items.  Ranking is wave-local and stable: wave w holds items
 //                    [w*64*IPT, (w+1)*64*IPT) of the tile as IPT rows of 64 consecutive items; per row the lanes
-//                    find their equals with 8 ballots (match-any), rank = running wave count of the digit (LDS) +
+//                    find their equals with 8 ballots (match-any: WAVE_MATCH, wave_prims.h), rank = running wave count of the digit (LDS) +
 //                    number of equal lanes below.  The per-digit tile counts then travel through a chained scan with
 //                    decoupled look-back: one 8-byte {flag, count} word per (tile, digit), published and polled
 //                    with relaxed agent-scope atomics (flag and value in ONE word, so no fences are needed and the
@@ -22,6 +22,7 @@
 //                    pair ids leave bare, no key does, and the tile offsets come from the band starts and histograms.
 // Traffic per pass: one read and one write of keys and values (+ 2 KB of status words per tile); packed: of one word.
 #include "radix_sort.h"
+#include "wave_prims.h"
 
 namespace {
 
@@ -53,15 +54,6 @@ template <typename K> struct Traits;
 template <> struct Traits<uint32_t> { static constexpr int IPT = RS_IPT32, IPT_S = 8; };
 template <> struct Traits<uint64_t> { static constexpr int IPT = 8, IPT_S = 4; };
 
-__device__ __forceinline__ int wave_incl_scan_u32(uint32_t v, int lane) {
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t t = __shfl_up(v, off);
-        if (lane >= off) v += t;
-    }
-    return v;
-}
-
 // value of lane q of this lane's quad (DPP quad_perm: one VALU move, no LDS)
 // value of lane q of this lane's PAIR (lanes 2k, 2k+1)
 __device__ __forceinline__ uint32_t pair_lane_u32(uint32_t v, int q) {
@@ -77,14 +69,30 @@ __device__ __forceinline__ uint32_t quad_lane_u32(uint32_t v, int q) {
     }
 }
 
+// The histogram kernels keep one private copy of their WORDS counters per wave (LDS atomics of different waves never meet on
+// an address): the clearing of all copies, and the flush -- the copies of the first `count` counters summed and added to dst,
+// zeros skipped.  The barriers around them are the kernels'.
+template <int WORDS>
+__device__ __forceinline__ void hist_clear(uint32_t (*sh)[WORDS]) {
+    for (int i = threadIdx.x; i < (HIST_THREADS / 64) * WORDS; i += HIST_THREADS) (&sh[0][0])[i] = 0;
+}
+template <int WORDS>
+__device__ __forceinline__ void hist_flush(const uint32_t (*sh)[WORDS], int count, uint32_t* __restrict__ dst) {
+    for (int i = threadIdx.x; i < count; i += HIST_THREADS) {
+        uint32_t t = 0;
+#pragma unroll
+        for (int w = 0; w < HIST_THREADS / 64; ++w) t += sh[w][i];
+        if (t) atomicAdd(&dst[i], t);
+    }
+}
+
 template <typename K>
 __global__ __launch_bounds__(HIST_THREADS) void k_rs_hist(const K* __restrict__ keys, int64_t n, int begin_bit,
                                                           int end_bit, int passes, uint32_t* __restrict__ hist,
                                                           const int32_t* __restrict__ n_dev) {
-    // one private copy of the histograms per wave: LDS atomics of different waves never meet on an address
     __shared__ uint32_t sh[HIST_THREADS / 64][MAX_PASSES * RADIX];
     if (n_dev) n = min(n, (int64_t)max(*n_dev, 0));   // the item count lives on the device; `n` is the launch capacity
-    for (int i = threadIdx.x; i < (HIST_THREADS / 64) * MAX_PASSES * RADIX; i += HIST_THREADS) (&sh[0][0])[i] = 0;
+    hist_clear(sh);
     __syncthreads();
     uint32_t* mine = sh[threadIdx.x >> 6];
     constexpr int CH = HIST_THREADS * HIST_ITEMS;
@@ -107,12 +115,7 @@ __global__ __launch_bounds__(HIST_THREADS) void k_rs_hist(const K* __restrict__ 
         }
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < passes * RADIX; i += HIST_THREADS) {
-        uint32_t t = 0;
-#pragma unroll
-        for (int w = 0; w < HIST_THREADS / 64; ++w) t += sh[w][i];
-        if (t) atomicAdd(&hist[(blockIdx.x & (HIST_COPIES - 1)) * (MAX_PASSES * RADIX) + i], t);   // copy b % HIST_COPIES: fewer adds meet on an address
-    }
+    hist_flush(sh, passes * RADIX, hist + (blockIdx.x & (HIST_COPIES - 1)) * (MAX_PASSES * RADIX));   // copy b % HIST_COPIES: fewer adds meet on an address
 }
 
 // Segmented, biased variant of the histogram (level-1 sort of the fused training calls): segment g = blockIdx.y holds the
@@ -127,7 +130,7 @@ __global__ __launch_bounds__(HIST_THREADS) void k_rs_hist_seg(const uint32_t* __
     __shared__ uint32_t sh[HIST_THREADS / 64][4 * RADIX];
     const uint32_t kmin = krange[0], ktop = krange[1];
     const int passes = (int)krange[2];
-    for (int i = threadIdx.x; i < (HIST_THREADS / 64) * 4 * RADIX; i += HIST_THREADS) (&sh[0][0])[i] = 0;
+    hist_clear(sh);
     __syncthreads();
     uint32_t* mine = sh[threadIdx.x >> 6];
     const uint32_t* kseg = keys + (int64_t)blockIdx.y * seg_n;
@@ -148,12 +151,7 @@ __global__ __launch_bounds__(HIST_THREADS) void k_rs_hist_seg(const uint32_t* __
         }
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < passes * RADIX; i += HIST_THREADS) {
-        uint32_t t = 0;
-#pragma unroll
-        for (int w = 0; w < HIST_THREADS / 64; ++w) t += sh[w][i];
-        if (t) atomicAdd(&hist[blockIdx.y * (MAX_PASSES * RADIX) + i], t);
-    }
+    hist_flush(sh, passes * RADIX, hist + blockIdx.y * (MAX_PASSES * RADIX));
 }
 
 // SEG (level-1 sort of the fused training calls; K = uint32_t): the input is n_seg segments of seg_n items (one per camera),
@@ -290,13 +288,7 @@ __global__ __launch_bounds__(THREADS) void k_rs_pass(const K* __restrict__ kin, 
     for (int i = 0; i < IPT; ++i) {
         const bool valid = wbase + i * 64 < tcount;
         const uint32_t d = (uint32_t)(key[i] >> shift) & dmask;
-        u64 m = __ballot(valid);
-#pragma unroll
-        for (int b = 0; b < RB; ++b) {
-            const bool bit = (d >> b) & 1u;
-            const u64 bal = __ballot(bit);
-            m &= bit ? bal : ~bal;
-        }
+        WAVE_MATCH(m, valid, d, RB)
         const uint32_t below = (uint32_t)__popcll(m & lt);
         const uint32_t prev = wh[d];
         if (valid && below == 0) wh[d] = prev + (uint32_t)__popcll(m);
@@ -319,8 +311,8 @@ __global__ __launch_bounds__(THREADS) void k_rs_pass(const K* __restrict__ kin, 
         tcnt[tid] = cnt;
     }
     // tile-local exclusive scan of the digit counts
-    const uint32_t inc = wave_incl_scan_u32(cnt, lane);
-    const uint32_t hinc = wave_incl_scan_u32(hv, lane);
+    const uint32_t inc = wave_incl_scan(cnt);
+    const uint32_t hinc = wave_incl_scan(hv);
     if (tid < RADIX && lane == 63) { wsum[w] = inc; hsum[w] = hinc; }
     __syncthreads();
     uint32_t hexc = 0;   // global base of bin `tid` (threads below RADIX)
@@ -433,51 +425,78 @@ inline SortShape band_shape(int64_t n) {
 }
 inline int sort_passes(int begin_bit, int end_bit) { return (end_bit - begin_bit + RB - 1) / RB; }
 
+// The scratch of a sort in SLOT_SORT_TMP: hist_words of histograms, MAX_PASSES ticket counters (one per pass), the status words
+// of the chained scans of `passes` passes over ntiles tiles and, behind this metadata, optional temporary keys and values.
+// The metadata is cleared here, once per sort.
+struct SortScratch { uint32_t* hist; uint32_t* counters; u64* status; void* tmp_keys; int32_t* tmp_vals; };
+int sort_scratch(st3r_ctx* ctx, hipStream_t s, size_t hist_words, int passes, int64_t ntiles, size_t tmp_key_bytes,
+                 size_t tmp_val_bytes, SortScratch* o) {
+    const size_t hist_bytes = align256(sizeof(uint32_t) * (hist_words + MAX_PASSES));
+    const size_t meta_bytes = hist_bytes + align256(sizeof(u64) * (size_t)passes * (size_t)ntiles * RADIX);
+    const size_t tk_bytes = align256(tmp_key_bytes);
+    ARENA_GET(SLOT_SORT_TMP, char, meta_bytes + tk_bytes + align256(tmp_val_bytes), base);
+    o->hist = (uint32_t*)base;
+    o->counters = o->hist + hist_words;
+    o->status = (u64*)(base + hist_bytes);
+    o->tmp_keys = base + meta_bytes;
+    o->tmp_vals = (int32_t*)(base + meta_bytes + tk_bytes);
+    HIP_TRY(hipMemsetAsync(base, 0, meta_bytes, s));
+    return ST3R_OK;
+}
+
+// One launch of k_rs_pass in the tile shape `sh` says: the arguments by name (those a form does not use stay zero), the
+// small or the large instantiation.  hist, status and counter are those of this pass.
+template <typename K>
+struct PassArgs {
+    const K* kin; const int32_t* vin; K* kout; int32_t* vout;
+    int64_t n; int shift, bits;
+    const uint32_t* hist; u64* status; uint32_t* counter;
+    const int32_t* n_dev;                                                               // count on the device
+    int64_t seg_n; int tiles_per_seg; const uint32_t* krange; int ps; K* ktmp; int32_t* vtmp;   // SEG
+    const uint32_t* band_tab; int n_bands;                                              // BAND
+};
+template <typename K, bool SEG = false, bool BAND = false, bool PACKED = false>
+void launch_pass(const SortShape& sh, hipStream_t s, const PassArgs<K>& a) {
+    if (sh.small)
+        hipLaunchKernelGGL((k_rs_pass<K, THREADS_S, Traits<K>::IPT_S, SEG, BAND, PACKED>), dim3((unsigned)sh.ntiles),
+                           dim3(THREADS_S), 0, s, a.kin, a.vin, a.kout, a.vout, a.n, a.shift, a.bits, a.hist, a.status, a.counter,
+                           a.n_dev, a.seg_n, a.tiles_per_seg, a.krange, a.ps, a.ktmp, a.vtmp, a.band_tab, a.n_bands);
+    else
+        hipLaunchKernelGGL((k_rs_pass<K, THREADS_L, Traits<K>::IPT, SEG, BAND, PACKED>), dim3((unsigned)sh.ntiles),
+                           dim3(THREADS_L), 0, s, a.kin, a.vin, a.kout, a.vout, a.n, a.shift, a.bits, a.hist, a.status, a.counter,
+                           a.n_dev, a.seg_n, a.tiles_per_seg, a.krange, a.ps, a.ktmp, a.vtmp, a.band_tab, a.n_bands);
+}
+
+// n_dev != NULL: the item count lives in device memory -- `n` sizes scratch and grids, the kernels sort the first
+// min(*n_dev, n) items (no host round trip between the kernel that counts the items and the sort)
 template <typename K>
 int sort_pairs(st3r_ctx* ctx, hipStream_t s, int64_t n, int begin_bit, int end_bit, const K* keys_in,
-               const int32_t* vals_in, K* keys_out, int32_t* vals_out, const int32_t* n_dev = nullptr) {
+               const int32_t* vals_in, K* keys_out, int32_t* vals_out, const int32_t* n_dev) {
     if (n == 0) return ST3R_OK;
     if (end_bit > (int)sizeof(K) * 8) end_bit = (int)sizeof(K) * 8;
     if (begin_bit < 0 || begin_bit >= end_bit) { st3r_set_error("radix sort: empty bit range"); return ST3R_ERR_INVALID; }
     const int passes = sort_passes(begin_bit, end_bit);
     const SortShape sh = sort_shape<K>(n);
-    const bool small = sh.small;
-    const int64_t ntiles = sh.ntiles;
-    const size_t hist_bytes = align256(sizeof(uint32_t) * (size_t)(HIST_COPIES * MAX_PASSES * RADIX + MAX_PASSES));
-    const size_t status_bytes = sizeof(u64) * (size_t)passes * (size_t)ntiles * RADIX;
-    const size_t meta_bytes = hist_bytes + align256(status_bytes);
     const bool need_tmp = passes > 1;
-    const size_t tk_bytes = need_tmp ? align256(sizeof(K) * (size_t)n) : 0;
-    const size_t tv_bytes = need_tmp && vals_in ? align256(sizeof(int32_t) * (size_t)n) : 0;
-    ARENA_GET(SLOT_SORT_TMP, char, meta_bytes + tk_bytes + tv_bytes, base);
-    uint32_t* hist = (uint32_t*)base;
-    uint32_t* counters = hist + HIST_COPIES * MAX_PASSES * RADIX;
-    u64* status = (u64*)(base + hist_bytes);
-    K* tk = (K*)(base + meta_bytes);
-    int32_t* tv = (int32_t*)(base + meta_bytes + tk_bytes);
-    HIP_TRY(hipMemsetAsync(base, 0, meta_bytes, s));
+    SortScratch sc;
+    int rc = sort_scratch(ctx, s, HIST_COPIES * MAX_PASSES * RADIX, passes, sh.ntiles, need_tmp ? sizeof(K) * (size_t)n : 0,
+                          need_tmp && vals_in ? sizeof(int32_t) * (size_t)n : 0, &sc);
+    if (rc) return rc;
     const int hist_blocks = (int)min((int64_t)1024, (n + HIST_THREADS * HIST_ITEMS - 1) / (HIST_THREADS * HIST_ITEMS));
     hipLaunchKernelGGL(k_rs_hist<K>, dim3(hist_blocks), dim3(HIST_THREADS), 0, s, keys_in, n, begin_bit, end_bit, passes,
-                       hist, n_dev);
-    const K* kin = keys_in;
-    const int32_t* vin = vals_in;
+                       sc.hist, n_dev);
+    PassArgs<K> a = {};
+    a.kin = keys_in; a.vin = vals_in; a.n = n; a.n_dev = n_dev;
     for (int ps = 0; ps < passes; ++ps) {
         // the last pass writes the caller's output; before that the passes alternate between it and the scratch
         const bool to_out = ((passes - 1 - ps) & 1) == 0;
-        K* ko = to_out ? keys_out : tk;
-        int32_t* vo = to_out ? vals_out : tv;
-        const int shift = begin_bit + RB * ps;
-        const int bits = min(RB, end_bit - shift);
-        if (small)
-            hipLaunchKernelGGL((k_rs_pass<K, THREADS_S, Traits<K>::IPT_S>), dim3((unsigned)ntiles), dim3(THREADS_S), 0, s, kin,
-                               vin, ko, vin ? vo : nullptr, n, shift, bits, hist + ps * RADIX,
-                               status + (size_t)ps * ntiles * RADIX, counters + ps, n_dev);
-        else
-            hipLaunchKernelGGL((k_rs_pass<K, THREADS_L, Traits<K>::IPT>), dim3((unsigned)ntiles), dim3(THREADS_L), 0, s, kin,
-                               vin, ko, vin ? vo : nullptr, n, shift, bits, hist + ps * RADIX,
-                               status + (size_t)ps * ntiles * RADIX, counters + ps, n_dev);
-        kin = ko;
-        if (vin) vin = vo;
+        a.kout = to_out ? keys_out : (K*)sc.tmp_keys;
+        a.vout = !vals_in ? nullptr : to_out ? vals_out : sc.tmp_vals;
+        a.shift = begin_bit + RB * ps;
+        a.bits = min(RB, end_bit - a.shift);
+        a.hist = sc.hist + ps * RADIX; a.status = sc.status + (size_t)ps * sh.ntiles * RADIX; a.counter = sc.counters + ps;
+        launch_pass<K>(sh, s, a);
+        a.kin = a.kout; a.vin = a.vout;
     }
     LAUNCH_CHECK();
     return ST3R_OK;
@@ -492,33 +511,19 @@ int sort_pairs_seg(st3r_ctx* ctx, hipStream_t s, int64_t seg_n, int n_seg, const
     constexpr int PASSES = 4;   // launches; the passes that run: krange[2]
     const int64_t n = seg_n * n_seg;
     const SortShape sh = sort_shape<K>(n, seg_n, n_seg);
-    const bool small = sh.small;
-    const int tiles_per_seg = sh.tiles_per_seg;
-    const int64_t ntiles = sh.ntiles;
-    const size_t hist_bytes = align256(sizeof(uint32_t) * ((size_t)n_seg * MAX_PASSES * RADIX + MAX_PASSES));
-    const size_t status_bytes = sizeof(u64) * (size_t)PASSES * (size_t)ntiles * RADIX;
-    const size_t meta_bytes = hist_bytes + align256(status_bytes);
-    const size_t tk_bytes = align256(sizeof(K) * (size_t)n), tv_bytes = align256(sizeof(int32_t) * (size_t)n);
-    ARENA_GET(SLOT_SORT_TMP, char, meta_bytes + tk_bytes + tv_bytes, base);
-    uint32_t* hist = (uint32_t*)base;
-    uint32_t* counters = hist + (size_t)n_seg * MAX_PASSES * RADIX;
-    u64* status = (u64*)(base + hist_bytes);
-    K* tk = (K*)(base + meta_bytes);
-    int32_t* tv = (int32_t*)(base + meta_bytes + tk_bytes);
-    HIP_TRY(hipMemsetAsync(base, 0, meta_bytes, s));
+    SortScratch sc;
+    int rc = sort_scratch(ctx, s, (size_t)n_seg * MAX_PASSES * RADIX, PASSES, sh.ntiles, sizeof(K) * (size_t)n,
+                          sizeof(int32_t) * (size_t)n, &sc);
+    if (rc) return rc;
     const int hist_blocks = (int)std::max<int64_t>(1, std::min<int64_t>(1024 / n_seg, (seg_n + HIST_THREADS * HIST_ITEMS - 1) / (HIST_THREADS * HIST_ITEMS)));
-    hipLaunchKernelGGL(k_rs_hist_seg, dim3(hist_blocks, n_seg), dim3(HIST_THREADS), 0, s, keys_in, seg_n, hist, krange);
+    hipLaunchKernelGGL(k_rs_hist_seg, dim3(hist_blocks, n_seg), dim3(HIST_THREADS), 0, s, keys_in, seg_n, sc.hist, krange);
+    PassArgs<K> a = {};
+    a.kin = keys_in; a.vin = vals_in; a.kout = keys_out; a.vout = vals_out; a.n = n; a.bits = RB;
+    a.seg_n = seg_n; a.tiles_per_seg = sh.tiles_per_seg; a.krange = krange; a.ktmp = (K*)sc.tmp_keys; a.vtmp = sc.tmp_vals;
     for (int ps = 0; ps < PASSES; ++ps) {
-        if (small)
-            hipLaunchKernelGGL((k_rs_pass<K, THREADS_S, Traits<K>::IPT_S, true>), dim3((unsigned)ntiles), dim3(THREADS_S), 0, s,
-                               keys_in, vals_in, keys_out, vals_out, n, 0, RB, hist + ps * RADIX,
-                               status + (size_t)ps * ntiles * RADIX, counters + ps, (const int32_t*)nullptr, seg_n,
-                               tiles_per_seg, krange, ps, tk, tv);
-        else
-            hipLaunchKernelGGL((k_rs_pass<K, THREADS_L, Traits<K>::IPT, true>), dim3((unsigned)ntiles), dim3(THREADS_L), 0, s,
-                               keys_in, vals_in, keys_out, vals_out, n, 0, RB, hist + ps * RADIX,
-                               status + (size_t)ps * ntiles * RADIX, counters + ps, (const int32_t*)nullptr, seg_n,
-                               tiles_per_seg, krange, ps, tk, tv);
+        a.ps = ps;
+        a.hist = sc.hist + ps * RADIX; a.status = sc.status + (size_t)ps * sh.ntiles * RADIX; a.counter = sc.counters + ps;
+        launch_pass<K, true>(sh, s, a);
     }
     LAUNCH_CHECK();
     return ST3R_OK;
@@ -548,7 +553,7 @@ __global__ __launch_bounds__(HIST_THREADS) void k_rs_hist_band(const uint32_t* _
     for (int b = lo; b < n_bands && (int64_t)s_start[b] < r1; ++b) {
         const int64_t a0 = max(r0, (int64_t)s_start[b]), a1 = min(r1, (int64_t)s_start[b + 1]);
         if (a0 >= a1) continue;   // uniform
-        for (int i = threadIdx.x; i < (HIST_THREADS / 64) * RADIX; i += HIST_THREADS) (&sh[0][0])[i] = 0;
+        hist_clear(sh);
         __syncthreads();
         for (int64_t base = a0; base < a1; base += CH) {
             uint32_t k[HIST_ITEMS];
@@ -562,12 +567,7 @@ __global__ __launch_bounds__(HIST_THREADS) void k_rs_hist_band(const uint32_t* _
                 if (base + i * HIST_THREADS + threadIdx.x < a1) atomicAdd(&mine[(k[i] >> shift) & (RADIX - 1)], 1u);
         }
         __syncthreads();
-        for (int i = threadIdx.x; i < RADIX; i += HIST_THREADS) {
-            uint32_t t = 0;
-#pragma unroll
-            for (int w = 0; w < HIST_THREADS / 64; ++w) t += sh[w][i];
-            if (t) atomicAdd(&hist[(size_t)b * RADIX + i], t);
-        }
+        hist_flush(sh, RADIX, hist + (size_t)b * RADIX);
         __syncthreads();
     }
 }
@@ -582,7 +582,7 @@ __global__ __launch_bounds__(RADIX) void k_band_offsets(const uint32_t* __restri
     __shared__ uint32_t s_wsum[RADIX / 64];
     const int b = blockIdx.x, d = threadIdx.x, lane = d & 63, w = d >> 6;
     const uint32_t h = hist[(size_t)b * RADIX + d];
-    const uint32_t inc = wave_incl_scan_u32(h, lane);
+    const uint32_t inc = wave_incl_scan(h);
     if (lane == 63) s_wsum[w] = inc;
     __syncthreads();
     uint32_t excl = inc - h;
@@ -601,37 +601,30 @@ int sort_pairs_banded(st3r_ctx* ctx, hipStream_t s, int64_t n, int n_bands, cons
     if (n == 0) return ST3R_OK;
     typedef uint32_t K;
     if (n_bands < 1 || n_bands > BAND_TAB - 1) { st3r_set_error("banded radix sort: 1 .. 256 bands"); return ST3R_ERR_INVALID; }
-    const SortShape sh = band_shape(n);
-    const int64_t ntiles = n / sh.tile + n_bands;   // every band may end in a ragged tile
-    const size_t hist_bytes = align256(sizeof(uint32_t) * ((size_t)n_bands * RADIX + MAX_PASSES));
-    const size_t status_bytes = sizeof(u64) * (size_t)ntiles * RADIX;
-    const size_t meta_bytes = hist_bytes + align256(status_bytes);
-    ARENA_GET(SLOT_SORT_TMP, char, meta_bytes, base);
-    uint32_t* hist = (uint32_t*)base;
-    uint32_t* counters = hist + (size_t)n_bands * RADIX;
-    u64* status = (u64*)(base + hist_bytes);
-    HIP_TRY(hipMemsetAsync(base, 0, meta_bytes, s));
+    SortShape sh = band_shape(n);
+    sh.ntiles = n / sh.tile + n_bands;   // every band may end in a ragged tile
+    SortScratch sc;
+    int rc = sort_scratch(ctx, s, (size_t)n_bands * RADIX, 1, sh.ntiles, 0, 0, &sc);
+    if (rc) return rc;
     constexpr int CH = HIST_THREADS * HIST_ITEMS;
     // (2048 ranges: with 1024 a workgroup walked eight 4096-key chunks plus the ragged ones at its band edges, one latency
     // after the other: 72 us at 26 M keys)
     const int hist_blocks = (int)std::min<int64_t>(2048, (n + CH - 1) / CH);
     const int64_t per = ((n + hist_blocks - 1) / hist_blocks + CH - 1) / CH * CH;
     const bool packed = packed_hist != nullptr;
-    hipLaunchKernelGGL(k_rs_hist_band, dim3(hist_blocks), dim3(HIST_THREADS), 0, s, keys_in, per, band_tab, n_bands, hist,
+    hipLaunchKernelGGL(k_rs_hist_band, dim3(hist_blocks), dim3(HIST_THREADS), 0, s, keys_in, per, band_tab, n_bands, sc.hist,
                        packed ? 24 : 0);
-    // (one argument list for the four instantiations; packed: shift 24, no value input, no key output)
-#define RS_BAND_PASS(THREADS, IPT, PACKED)                                                                                    \
-    hipLaunchKernelGGL((k_rs_pass<K, THREADS, IPT, false, true, PACKED>), dim3((unsigned)ntiles), dim3(THREADS), 0, s, keys_in,   \
-                       PACKED ? (const int32_t*)nullptr : vals_in, PACKED ? (K*)nullptr : keys_out, vals_out, n,              \
-                       PACKED ? 24 : 0, RB, hist, status, counters, (const int32_t*)nullptr, (int64_t)0, 0,                   \
-                       (const uint32_t*)nullptr, 0, (K*)nullptr, (int32_t*)nullptr, band_tab, n_bands)
-    if (packed) {
-        if (sh.small) RS_BAND_PASS(THREADS_S, Traits<K>::IPT_S, true); else RS_BAND_PASS(THREADS_L, Traits<K>::IPT, true);
-        *packed_hist = hist;
+    PassArgs<K> a = {};
+    a.kin = keys_in; a.vout = vals_out; a.n = n; a.bits = RB; a.hist = sc.hist; a.status = sc.status; a.counter = sc.counters;
+    a.band_tab = band_tab; a.n_bands = n_bands;
+    if (packed) {   // shift 24, no value input, no key output
+        a.shift = 24;
+        launch_pass<K, false, true, true>(sh, s, a);
+        *packed_hist = sc.hist;
     } else {
-        if (sh.small) RS_BAND_PASS(THREADS_S, Traits<K>::IPT_S, false); else RS_BAND_PASS(THREADS_L, Traits<K>::IPT, false);
+        a.vin = vals_in; a.kout = keys_out;
+        launch_pass<K, false, true>(sh, s, a);
     }
-#undef RS_BAND_PASS
     LAUNCH_CHECK();
     return ST3R_OK;
 }
@@ -674,19 +667,11 @@ int st3r_radix_sort_u32_segments(st3r_ctx* ctx, hipStream_t s, int64_t seg_n, in
 }
 
 int st3r_radix_sort_u32(st3r_ctx* ctx, hipStream_t s, int64_t n, int begin_bit, int end_bit, const uint32_t* keys_in,
-                        const int32_t* vals_in, uint32_t* keys_out, int32_t* vals_out) {
-    return sort_pairs<uint32_t>(ctx, s, n, begin_bit, end_bit, keys_in, vals_in, keys_out, vals_out);
+                        const int32_t* vals_in, uint32_t* keys_out, int32_t* vals_out, const int32_t* n_dev) {
+    return sort_pairs<uint32_t>(ctx, s, n, begin_bit, end_bit, keys_in, vals_in, keys_out, vals_out, n_dev);
 }
 
 int st3r_radix_sort_u64(st3r_ctx* ctx, hipStream_t s, int64_t n, int begin_bit, int end_bit, const uint64_t* keys_in,
                         const int32_t* vals_in, uint64_t* keys_out, int32_t* vals_out) {
-    return sort_pairs<uint64_t>(ctx, s, n, begin_bit, end_bit, keys_in, vals_in, keys_out, vals_out);
-}
-
-// the same with the item count in device memory: `n_cap` sizes scratch and grids, the kernels sort the first
-// min(*n_dev, n_cap) items (no host round trip between the kernel that counts the items and the sort)
-int st3r_radix_sort_u32_devcount(st3r_ctx* ctx, hipStream_t s, int64_t n_cap, const int32_t* n_dev, int begin_bit,
-                                 int end_bit, const uint32_t* keys_in, const int32_t* vals_in, uint32_t* keys_out,
-                                 int32_t* vals_out) {
-    return sort_pairs<uint32_t>(ctx, s, n_cap, begin_bit, end_bit, keys_in, vals_in, keys_out, vals_out, n_dev);
+    return sort_pairs<uint64_t>(ctx, s, n, begin_bit, end_bit, keys_in, vals_in, keys_out, vals_out, nullptr);
 }

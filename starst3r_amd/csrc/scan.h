@@ -4,6 +4,7 @@
 // arithmetic: the result does not depend on the grouping.  In-place operation is allowed (out == in).
 #pragma once
 #include "common.h"
+#include "wave_prims.h"
 
 namespace st3r_scan {
 
@@ -11,54 +12,29 @@ constexpr int THREADS = 256;
 constexpr int ITEMS = 8;
 constexpr int TILE = THREADS * ITEMS;
 
-template <typename T>
-__device__ __forceinline__ T wave_incl(T v, int lane) {
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const T t = __shfl_up(v, off);
-        if (lane >= off) v += t;
-    }
-    return v;
-}
-
-// inclusive scan of one value per thread over the workgroup; *total = workgroup sum
-template <typename T>
-__device__ __forceinline__ T block_incl(T v, T* wsum, T* total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const T inc = wave_incl(v, lane);
-    if (lane == 63) wsum[w] = inc;
-    __syncthreads();
-    T base = 0;
-#pragma unroll
-    for (int i = 0; i < THREADS / 64; ++i) base += i < w ? wsum[i] : T(0);
-    *total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-    __syncthreads();
-    return inc + base;
-}
+static_assert(THREADS == 256, "block_incl_scan (wave_prims.h) is a scan over four waves");
 
 template <typename T>
 __global__ __launch_bounds__(THREADS) void k_reduce(const T* __restrict__ in, int64_t n, T* __restrict__ tile_sums) {
-    __shared__ T wsum[THREADS / 64];
     const int64_t base = (int64_t)blockIdx.x * TILE + (int64_t)threadIdx.x * ITEMS;
     T s = 0;
 #pragma unroll
     for (int i = 0; i < ITEMS; ++i)
         if (base + i < n) s += in[base + i];
     T total;
-    block_incl(s, wsum, &total);
+    block_incl_scan(s, &total);
     if (threadIdx.x == 0) tile_sums[blockIdx.x] = total;
 }
 
 // exclusive scan of the tile sums in place (one workgroup)
 template <typename T>
 __global__ __launch_bounds__(THREADS) void k_tile_sums(T* __restrict__ tile_sums, int n_tiles) {
-    __shared__ T wsum[THREADS / 64];
     T carry = 0;
     for (int b = 0; b < n_tiles; b += THREADS) {
         const int idx = b + threadIdx.x;
         const T v = idx < n_tiles ? tile_sums[idx] : T(0);
         T total;
-        const T inc = block_incl(v, wsum, &total);
+        const T inc = block_incl_scan(v, &total);
         if (idx < n_tiles) tile_sums[idx] = carry + inc - v;
         carry += total;
     }
@@ -66,14 +42,13 @@ __global__ __launch_bounds__(THREADS) void k_tile_sums(T* __restrict__ tile_sums
 
 template <typename T, bool EXCLUSIVE>
 __global__ __launch_bounds__(THREADS) void k_down(const T* in, int64_t n, const T* __restrict__ tile_sums, T* out) {
-    __shared__ T wsum[THREADS / 64];
     const int64_t base = (int64_t)blockIdx.x * TILE + (int64_t)threadIdx.x * ITEMS;
     T v[ITEMS];
     T s = 0;
 #pragma unroll
     for (int i = 0; i < ITEMS; ++i) { v[i] = base + i < n ? in[base + i] : T(0); s += v[i]; }
     T total;
-    const T inc = block_incl(s, wsum, &total);
+    const T inc = block_incl_scan(s, &total);
     T run = tile_sums[blockIdx.x] + inc - s;
 #pragma unroll
     for (int i = 0; i < ITEMS; ++i) {

@@ -75,7 +75,7 @@ int st3r_scan_tiles(int64_t n);
 void st3r_emit_grid(int N, int C, int* bpc, int* grid, int* self_base);
 void st3r_isect_constants(int64_t out[5]);
 // band_tile > 0: the banded emission (records split by the high byte of their key) and, in *band_table, the band starts and
-// sort tiles for st3r_sort_tile_banded_impl: two arrays of ST3R_BAND_TAB words (gs_isect.hip: k_band_table); tile_keys == NULL
+// sort tiles for st3r_radix_sort_u32_banded (radix_sort.h): two arrays of ST3R_BAND_TAB words (gs_isect.hip: k_band_table); tile_keys == NULL
 // (banded only, N * C <= 2^24): the packed form, vals = pair id | low key byte << 24 (st3r_radix_sort_u32_banded_packed)
 int st3r_isect_emit_chain_impl(st3r_ctx* ctx, hipStream_t s, int N, int C, const int32_t* perm, const void* rects,
                                int rect32, int tile_w, int tile_h, uint32_t* tile_keys, int32_t* vals, int64_t cap,
@@ -88,12 +88,9 @@ int st3r_isect_offsets32_impl(hipStream_t s, int64_t n_isects, const uint32_t* k
 int st3r_sort_tile_end_bit(int end_bit);
 int st3r_sort_tile_impl(st3r_ctx* ctx, hipStream_t s, int64_t n, int end_bit, uint32_t* keys_in, int32_t* vals_in,
                         uint32_t* keys_out, int32_t* vals_out, const int32_t* n_dev);
-// the banded tile sort (keys of 9 .. 16 bits, unless debug flag 16 asks for the two passes): does it apply, the items per
-// sort tile it will use for a capacity of n records, and the one low-byte pass over the banded stream
+// the banded tile sort (keys of 9 .. 16 bits, unless debug flag 16 asks for the two passes): does it apply?  (Its sort tile
+// and its one low-byte pass over the banded stream: radix_sort.h.)
 int st3r_sort_tile_banded(int end_bit, int debug_flags);
-int st3r_sort_tile_banded_tile(int64_t n);
-int st3r_sort_tile_banded_impl(st3r_ctx* ctx, hipStream_t s, int64_t n, int n_bands, const uint32_t* band_table,
-                               uint32_t* keys_in, int32_t* vals_in, uint32_t* keys_out, int32_t* vals_out);
 
 // ---- gs_blend.hip, gs_blend_cells.hip, gs_blend_depth.hip ----
 // end_in_offsets (fused calls): ro.offsets has C * tiles + 1 entries and the last one closes the last tile -- the record

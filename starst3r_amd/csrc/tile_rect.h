@@ -88,14 +88,25 @@ __device__ __forceinline__ void rect_store(void* rects, int is32, int64_t i, Til
     if (is32) reinterpret_cast<uint32_t*>(rects)[i] = pack_rect32(r);
     else reinterpret_cast<uint64_t*>(rects)[i] = pack_rect(r);
 }
-// entry i of either form: origin x0 | y0 << 16, width, height (is32 is uniform over the launch)
-__device__ __forceinline__ void rect_load(const void* rects, int is32, int64_t i, uint32_t* org, uint32_t* w, uint32_t* h) {
+// a packed word of either form: origin x0 | y0 << 16, width, height
+__device__ __forceinline__ void rect_decode(uint32_t r, uint32_t* org, uint32_t* w, uint32_t* h) {
+    *org = (r & 0xFFu) | ((r & 0xFF00u) << 8); *w = (r >> 16) & 0xFFu; *h = r >> 24;
+}
+__device__ __forceinline__ void rect_decode(uint64_t r, uint32_t* org, uint32_t* w, uint32_t* h) {
+    *org = (uint32_t)(r & 0xFFFFFFFFull); *w = (uint32_t)((r >> 32) & 0xFFFF); *h = (uint32_t)(r >> 48);
+}
+// entry i of either form, decoded (is32 is uniform over the launch); COPY: the raw word also goes to copy[j]
+template <bool COPY = false>
+__device__ __forceinline__ void rect_load(const void* rects, int is32, int64_t i, uint32_t* org, uint32_t* w, uint32_t* h,
+                                          void* copy = nullptr, int64_t j = 0) {
     if (is32) {
         const uint32_t r = reinterpret_cast<const uint32_t*>(rects)[i];
-        *org = (r & 0xFFu) | ((r & 0xFF00u) << 8); *w = (r >> 16) & 0xFFu; *h = r >> 24;
+        if (COPY) reinterpret_cast<uint32_t*>(copy)[j] = r;
+        rect_decode(r, org, w, h);
     } else {
         const uint64_t r = reinterpret_cast<const uint64_t*>(rects)[i];
-        *org = (uint32_t)(r & 0xFFFFFFFFull); *w = (uint32_t)((r >> 32) & 0xFFFF); *h = (uint32_t)(r >> 48);
+        if (COPY) reinterpret_cast<uint64_t*>(copy)[j] = r;
+        rect_decode(r, org, w, h);
     }
 }
 
