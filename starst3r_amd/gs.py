@@ -17,6 +17,9 @@ __all__ = (
     "train",
 )
 
+import contextlib
+import types
+
 import numpy as np
 import torch
 
@@ -420,11 +423,190 @@ def _per_view_moments(st, name, n, device):
         setattr(st, name + "_step", 0)
 
 
+def _frozen_rows_kept(new, old, frozen):
+    """`new` (the caller's own tensor) on old's device and in its dtype, the rows `frozen` taken from `old` bit for bit"""
+    new = new.to(device=old.device, dtype=old.dtype)
+    if frozen:
+        new[frozen] = old.detach()[frozen]
+    return new
+
+
 def _single_replica_only(option, scene, enable_pruning):
     """the refusal of a per-view option (named as the user spelled it) under torch.distributed or the sharded layout"""
     if _dist.rank_world()[1] > 1 or _sharded_layout(scene, 1, enable_pruning):
         raise NotImplementedError(f"{option} != 0 is supported in a single process with replicated Gaussians only "
                                   "(not under torch.distributed, not with ST3R_MULTI_GPU=gaussian-sharded)")
+
+
+class _PerViewOption:
+    """One per-view option of run_3dgs_optim: everything the call does for it.  run_3dgs_optim builds the options that are
+    on (when_on) and walks them at each of the hooks below; an option overrides those it needs.  `c` is what the call
+    works on: scene, ctx, st (scene._gs_optim), views, width, height, gt, and the w2c and Ks of the views, which an option
+    that trains them replaces by a private copy."""
+    spelled = None     # the rate or factor that switches it on, as the user spells it
+    schedule = True    # may that value be a callable step -> float
+    counter = None     # name of its Adam step counter on scene._gs_optim: moves wherever st.step moves
+
+    @classmethod
+    def when_on(cls, scene, enable_pruning, value, *args):
+        """the option's object, refused or checked before anything runs -- None when `value` leaves it off"""
+        if not _on(value, schedule=cls.schedule):
+            return None
+        _single_replica_only(cls.spelled, scene, enable_pruning)
+        return cls(scene, value, *args)
+
+    def set_up(self, c):
+        """once c.views, c.w2c, c.Ks and c.gt exist: private copies, moments, masks, buffers"""
+
+    def register(self, c):
+        """with the ctx, for the duration of the call"""
+
+    def clear(self, c):
+        """what register registered"""
+
+    def behind_step(self, c, step):
+        """its own launch behind iteration `step`'s training step, on the same stream"""
+
+    def finish(self, c):
+        """whatever ends the loop: what the scene gets back"""
+
+
+class _DepthPrior(_PerViewOption):
+    """depth_fac: the views' depth maps and 0/1 weights, registered with the ctx for the fused step's depth term"""
+    spelled, schedule = "depth_fac", False
+
+    def __init__(self, scene, depth_fac, conf_thres):
+        self.fac, self.conf_thres = float(depth_fac), conf_thres
+
+    def set_up(self, c):
+        self.prior, self.weights = _depth_prior_on_device(c.scene, c.views, self.conf_thres, c.height, c.width)
+
+    def register(self, c):
+        ops.set_depth_prior(c.ctx, c.gt, self.prior, self.weights, self.fac)
+
+    def clear(self, c):
+        ops.set_depth_prior(c.ctx, None, None, None)
+
+
+class _Poses(_PerViewOption):
+    """pose_lr: the step itself moves the cameras (ops.train_step_poses, with step_args); scene.c2w follows at the end"""
+    spelled, counter = "pose_lr", "pose_step"
+
+    def __init__(self, scene, pose_lr, pose_freeze):
+        self.rate, self.freeze = pose_lr, pose_freeze
+
+    def set_up(self, c):
+        # a private copy: the tensor Scene.w2c caches is never trained (c.w2c may be a view of it)
+        c.w2c = c.w2c.clone()
+        n_cam = c.w2c.shape[0]
+        _per_view_moments(c.st, "pose", 6 * n_cam, c.w2c.device)   # (new when the views changed)
+        # pose_freeze is NOT validated like the other two freeze lists (_view_indices): its indices are taken modulo the
+        # number of cameras.  Kept as it is; tightening it would change behaviour.
+        self.frozen = sorted({int(i) % n_cam for i in self.freeze})
+        self.mask = _freeze_mask(n_cam, self.frozen, c.w2c.device)
+        c.st.pose_w2c = c.w2c   # the matrices being trained (diagnostics; scene.c2w follows when the loop ends)
+
+    def step_args(self, st, step):
+        """the arguments ops.train_step_poses takes behind ops.train_step's"""
+        return st.pose_m, st.pose_v, _rate_at(self.rate, step), st.pose_step, self.mask
+
+    def finish(self, c):   # a NEW c2w tensor, so that Scene.w2c's cache refreshes itself; inverted in double
+        c.scene.c2w = _frozen_rows_kept(torch.inverse(c.w2c.double()), c.scene.c2w, self.frozen)
+
+
+class _Exposures(_PerViewOption):
+    """exposure_lr: scene.exposures, trained in place by their own Adam behind the step, from the gradient the step
+    leaves in st.exp_grad"""
+    spelled, counter = "exposure_lr", "exp_step"
+
+    def __init__(self, scene, exposure_lr, exposure_freeze):
+        self.rate, self.frozen = exposure_lr, _exposure_frozen(len(scene.imgs), exposure_freeze)
+
+    def set_up(self, c):
+        scene, st, dev = c.scene, c.st, c.gt.device
+        n_img = len(scene.imgs)
+        E = getattr(scene, "exposures", None)
+        if E is None or tuple(E.shape) != (n_img, 3, 4):   # first use, or the number of images changed
+            E = torch.eye(3, 4, device=dev).repeat(n_img, 1, 1)
+        if E.dtype != torch.float32 or E.device != dev or not E.is_contiguous():
+            E = E.detach().to(dev, torch.float32).contiguous()
+        scene.exposures = E   # trained in place
+        _per_view_moments(st, "exp", 12 * n_img, dev)
+        st.exp_grad = torch.zeros((n_img, 3, 4), device=dev)   # this step's d loss / d exposures (diagnostics)
+        self.mask = _freeze_mask(n_img, self.frozen, dev)
+
+    def register(self, c):
+        ops.set_exposure(c.ctx, c.gt, c.scene.exposures, c.st.exp_grad)
+
+    def clear(self, c):
+        ops.set_exposure(c.ctx, None, None, None)
+
+    def behind_step(self, c, step):   # behind the same device-side guard as the step's updates
+        st = c.st
+        ops.exposure_adam_step(c.ctx, c.scene.exposures, st.exp_grad, st.exp_m, st.exp_v, _rate_at(self.rate, step),
+                               st.betas[0], st.betas[1], st.eps, st.exp_step, self.mask)
+
+
+class _Intrinsics(_PerViewOption):
+    """scene.intrinsics_lr: a private copy of the views' intrinsics, trained in place by its own Adam behind the step, which
+    wrote st.k_grad at the intrinsics it started with; scene.intrinsics follows at the end"""
+    spelled, counter = "scene.intrinsics_lr", "k_step"
+
+    def __init__(self, scene, intrinsics_lr):
+        self.rate = intrinsics_lr
+        self.frozen = _view_indices(len(scene.imgs), getattr(scene, "intrinsics_freeze", ()), "scene.intrinsics_freeze")
+        self.tie_focal = bool(getattr(scene, "intrinsics_tie_focal", True))
+        self.opt_pp = bool(getattr(scene, "intrinsics_opt_pp", False))
+
+    def set_up(self, c):
+        c.Ks = c.Ks.clone()   # a private copy, trained in place
+        n_k = c.Ks.shape[0]
+        _per_view_moments(c.st, "k", 4 * n_k, c.Ks.device)   # (new when the views changed)
+        c.st.k_grad = torch.zeros((n_k, 4), device=c.Ks.device)   # this step's d loss / d (fx, fy, cx, cy) (diagnostics)
+        self.mask = _freeze_mask(n_k, self.frozen, c.Ks.device)
+
+    def register(self, c):
+        ops.set_intrinsics_grad(c.ctx, c.gt, c.st.k_grad)
+
+    def clear(self, c):
+        ops.set_intrinsics_grad(c.ctx, None, None)
+
+    def behind_step(self, c, step):
+        st = c.st
+        ops.intrinsics_adam_step(c.ctx, c.Ks, st.k_grad, st.k_m, st.k_v, _rate_at(self.rate, step), st.betas[0],
+                                 st.betas[1], st.eps, st.k_step, self.mask, c.width, c.height, self.tie_focal, self.opt_pp)
+
+    def finish(self, c):   # a NEW intrinsics tensor (the private copy), device and dtype as before
+        c.scene.intrinsics = _frozen_rows_kept(c.Ks, c.scene.intrinsics, self.frozen)
+
+
+def _iterations(iters, verbose):
+    """range(iters), with a progress bar when verbose"""
+    if verbose:
+        from tqdm import trange
+        return trange(iters)
+    return range(iters)
+
+
+@contextlib.contextmanager
+def _registered(c, options=()):
+    """What is registered with c.ctx belongs to the call: the moments of the ground truth c.gt, then the options' buffers --
+    cleared in that order whatever ends the block, a failing registration included."""
+    try:
+        ops.set_gt_moments(c.ctx, c.gt, _gt_moments(c.scene, c.ctx, c.gt))
+        for o in options:
+            o.register(c)
+        yield
+    finally:
+        ops.set_gt_moments(c.ctx, None, None)
+        for o in options:
+            o.clear(c)
+
+
+def _losses_list(losses, iters):
+    """the per-iteration losses summed over the ranks: one device->host copy for the whole call (reference: .item() per step)"""
+    _dist.all_reduce_sum(losses)
+    return losses[:iters].cpu().tolist()
 
 
 def run_3dgs_optim(
@@ -488,23 +670,13 @@ def run_3dgs_optim(
     together with pose_lr, depth_fac, exposure_lr and enable_pruning; single process, Gaussians replicated only.  With
     intrinsics_lr == 0 nothing about the call changes and scene.intrinsics is not touched.
     """
-    poses_on, depth_on = _on(pose_lr, schedule=True), _on(depth_fac)
-    if depth_on:
-        _single_replica_only("depth_fac", scene, enable_pruning)
-    if poses_on:
-        _single_replica_only("pose_lr", scene, enable_pruning)
-    exposure_on = _on(exposure_lr, schedule=True)
-    if exposure_on:   # (checked before anything runs)
-        _single_replica_only("exposure_lr", scene, enable_pruning)
-        exp_frozen = _exposure_frozen(len(scene.imgs), exposure_freeze)
-    intrinsics_lr = getattr(scene, "intrinsics_lr", 0.0)
-    intrinsics_freeze = getattr(scene, "intrinsics_freeze", ())
-    intrinsics_tie_focal = getattr(scene, "intrinsics_tie_focal", True)
-    intrinsics_opt_pp = getattr(scene, "intrinsics_opt_pp", False)
-    intrinsics_on = _on(intrinsics_lr, schedule=True)
-    if intrinsics_on:   # (checked before anything runs)
-        _single_replica_only("scene.intrinsics_lr", scene, enable_pruning)
-        k_frozen = _view_indices(len(scene.imgs), intrinsics_freeze, "scene.intrinsics_freeze")
+    depth = _DepthPrior.when_on(scene, enable_pruning, depth_fac, depth_conf_thres)
+    poses = _Poses.when_on(scene, enable_pruning, pose_lr, pose_freeze)
+    exposures = _Exposures.when_on(scene, enable_pruning, exposure_lr, exposure_freeze)
+    intrinsics = _Intrinsics.when_on(scene, enable_pruning, getattr(scene, "intrinsics_lr", 0.0))
+    # in this order at every hook: checks (above), set-up, registration, clearing, behind the step, finish
+    options = [o for o in (depth, poses, exposures, intrinsics) if o is not None]
+    counters = [o.counter for o in options if o.counter]
     height, width = scene.imgs[0].shape[:2]
     ctx = ops.get_context(scene.device)
     st = scene._gs_optim
@@ -514,40 +686,16 @@ def run_3dgs_optim(
         return _run_3dgs_optim_sharded(scene, iters, loss_ssim_fac, loss_opacity_fac, loss_scale_fac, verbose,
                                        enable_pruning)
     views = _dist.shard_views(len(scene.imgs), rank, world)
-    w2c_all = scene.w2c.to(scene.device, torch.float32)
-    w2c = w2c_all[views].contiguous()
+    w2c = scene.w2c.to(scene.device, torch.float32)[views].contiguous()
     Ks = scene.intrinsics.to(scene.device, torch.float32)[views].contiguous()
     campos = ops.camera_positions(w2c)
-    if depth_on:   # (checked before anything runs)
-        prior, prior_w = _depth_prior_on_device(scene, views, depth_conf_thres, height, width)
     gt = _gt_on_device(scene, views)
     losses = torch.zeros(max(iters, 1), device=scene.device)
     fused = world == 1 or getattr(ctx, "native_comm", False)
-    if poses_on:
-        # a private copy: the tensor Scene.w2c caches is never trained (w2c_all may BE that tensor)
-        w2c = w2c.clone()
-        n_cam = w2c.shape[0]
-        _per_view_moments(st, "pose", 6 * n_cam, w2c.device)   # (new when the views changed)
-        frozen = sorted({int(i) % n_cam for i in pose_freeze})
-        pose_mask = _freeze_mask(n_cam, frozen, w2c.device)
-        st.pose_w2c = w2c   # the matrices being trained (diagnostics; scene.c2w follows when the loop ends)
-    if exposure_on:
-        n_img = len(scene.imgs)
-        E = getattr(scene, "exposures", None)
-        if E is None or tuple(E.shape) != (n_img, 3, 4):   # first use, or the number of images changed
-            E = torch.eye(3, 4, device=gt.device).repeat(n_img, 1, 1)
-        if E.dtype != torch.float32 or E.device != gt.device or not E.is_contiguous():
-            E = E.detach().to(gt.device, torch.float32).contiguous()
-        scene.exposures = E   # trained in place
-        _per_view_moments(st, "exp", 12 * n_img, gt.device)
-        st.exp_grad = torch.zeros((n_img, 3, 4), device=gt.device)   # this step's d loss / d exposures (diagnostics)
-        exp_mask = _freeze_mask(n_img, exp_frozen, gt.device)
-    if intrinsics_on:
-        Ks = Ks.clone()   # a private copy, trained in place; scene.intrinsics follows when the loop ends
-        n_k = Ks.shape[0]
-        _per_view_moments(st, "k", 4 * n_k, Ks.device)   # (new when the views changed)
-        st.k_grad = torch.zeros((n_k, 4), device=Ks.device)   # this step's d loss / d (fx, fy, cx, cy) (diagnostics)
-        k_mask = _freeze_mask(n_k, k_frozen, Ks.device)
+    c = types.SimpleNamespace(scene=scene, ctx=ctx, st=st, views=views, width=width, height=height, gt=gt, w2c=w2c, Ks=Ks)
+    for o in options:
+        o.set_up(c)
+    w2c, Ks = c.w2c, c.Ks   # (the private copies of the options that train them)
     restore_exchange = None
     if enable_pruning and fused and world > 1 and ops.get_exchange(ctx) in ("rs_ag", "direct"):
         # reduce-scatter exchange (through RCCL or through the peers' exported buffers): a rank maintains the Adam moments of its piece of the buffer only; growing the set
@@ -555,10 +703,6 @@ def run_3dgs_optim(
         # the pieces are all-gathered first so that every rank holds the same, complete moments
         ops.allgather_pieces(ctx, st.m); ops.allgather_pieces(ctx, st.v)
         restore_exchange = ops.set_exchange(ctx, "allreduce")
-    it_range = range(iters)
-    if verbose:
-        from tqdm import trange
-        it_range = trange(iters)
     # The kernels touch SH rows 0..3 only (sh_degree = 1, gs.py:81,86).  Read in place those 48 bytes sit at a 288-byte
     # stride -- three streaming kernels (projection, its backward, Adam) then move ~2.7x the SH bytes they use --, so the loop
     # trains a COMPACT copy [N, 4, 3] (sh_stride = 12) and writes it back into rows 0..3 of `shN` when it ends, and before
@@ -574,11 +718,11 @@ def run_3dgs_optim(
             sh_c[0] = g["shN"].data[:, :4].contiguous()
         P = {k: g[k].data for k in ("means", "quats", "scales", "opacities")}  # growth replaces the tensors
         P["shN"] = sh_c[0]
-        if poses_on:   # the same single call, and the cameras move in it too (w2c and campos in place)
+        # which step call: the one branch on a specific option, because that is how the C interface is shaped
+        if poses is not None:   # the same single call, and the cameras move in it too (w2c and campos in place)
             ops.train_step_poses(ctx, P, w2c, Ks, campos, gt, width, height, loss_ssim_fac, loss_opacity_fac,
                                  loss_scale_fac, st.grads, st.m, st.v, st.lr, st.betas[0], st.betas[1], st.eps, st.step,
-                                 losses[step:step + 1], st.pose_m, st.pose_v,
-                                 _rate_at(pose_lr, step), st.pose_step, pose_mask, want_stats=False)
+                                 losses[step:step + 1], *poses.step_args(st, step), want_stats=False)
         elif fused:   # the whole iteration is one C call (gradient all-reduce inside, over the ctx's communicator)
             # no host round trip in steady state (single rank; with a communicator the library sizes every step exactly)
             ops.train_step(ctx, P, w2c, Ks, campos, gt, width, height, loss_ssim_fac, loss_opacity_fac,
@@ -590,111 +734,76 @@ def run_3dgs_optim(
                               loss_scale_fac, st.grads, losses[step:step + 1], want_stats=True)
             _dist.all_reduce_sum(st.grads)
             ops.adam_step(ctx, P, st.grads, st.m, st.v, st.lr, st.betas[0], st.betas[1], st.eps, st.step)
-        if exposure_on:   # behind the step on the same stream, and behind the same device-side guard as its updates
-            ops.exposure_adam_step(ctx, scene.exposures, st.exp_grad, st.exp_m, st.exp_v, _rate_at(exposure_lr, step),
-                                   st.betas[0], st.betas[1], st.eps, st.exp_step, exp_mask)
-        if intrinsics_on:   # the same: behind the step, which wrote st.k_grad at the intrinsics it started with
-            ops.intrinsics_adam_step(ctx, Ks, st.k_grad, st.k_m, st.k_v, _rate_at(intrinsics_lr, step), st.betas[0],
-                                     st.betas[1], st.eps, st.k_step, k_mask, width, height, bool(intrinsics_tie_focal),
-                                     bool(intrinsics_opt_pp))
+        for o in options:
+            o.behind_step(c, step)
 
     def capacity_error(e):
         return getattr(e, "code", 0) == -3 and world == 1
 
-    def count_step(d):   # the pose step counter moves wherever the Gaussians' does
+    def count_step(d):   # the options' step counters move wherever the Gaussians' does
         st.step += d
-        if poses_on:
-            st.pose_step += d
-        if exposure_on:
-            st.exp_step += d
-        if intrinsics_on:
-            st.k_step += d
+        for name in counters:
+            setattr(st, name, getattr(st, name) + d)
 
     # A peer failure (ST3R_ERR_PEER: the step before failed on some rank, nobody applied it) ABORTS the run on every rank
     # alike -- all ranks get the code from the same call --; the exchange form is restored whatever ends the loop.
     # our own strategy reads the parameters in step_post_backward only, and the SH rows on refinement steps only
     # (relocation / growth copy whole rows); any OTHER strategy object sees up-to-date rows at every hook call
     own_strategy = type(scene.strategy) is MCMCStrategy
-    try:   # what is registered belongs to this call: cleared below whatever ends the loop, a failing registration included
-        ops.set_gt_moments(ctx, gt, _gt_moments(scene, ctx, gt))
-        if depth_on:
-            ops.set_depth_prior(ctx, gt, prior, prior_w, float(depth_fac))
-        if exposure_on:   # and so do the exposures
-            ops.set_exposure(ctx, gt, scene.exposures, st.exp_grad)
-        if intrinsics_on:
-            ops.set_intrinsics_grad(ctx, gt, st.k_grad)
-        step = 0
-        for _ in it_range:
-            if enable_pruning:
-                if not own_strategy:
-                    sh_write_back()
-                scene.strategy.step_pre_backward(g, scene.optimizers, scene.strategy_state, step, None)
-                if not own_strategy:
-                    sh_c[0] = g["shN"].data[:, :4].contiguous()
-            count_step(1)
-            try:
-                one_iteration(step)
-            except _lib_mod.St3rError as e:
-                # ST3R_ERR_CAPACITY is reported by the call AFTER the asynchronous step that outgrew its buffers (> 25 % more
-                # tile intersections than the step before it).  That step's records past the capacity were dropped and its
-                # Adam update was skipped on the device (k_adam's guard), so no parameter update has to be undone: the lost
-                # iteration is repeated -- the context is back on the exactly sized path -- and then this one runs.  With
-                # enable_pruning the strategy hooks of the lost iteration have already run on the un-updated parameters
-                # (its position noise, and on a refinement step its relocation / growth): they are NOT run again, i.e. the
-                # noise of that one iteration is drawn before its update instead of after it.  A deviation of one step's
-                # noise (tests/test_gpu_api.py::test_run_3dgs_optim_repeats_...); overflows need > 25 % more tile
-                # intersections than the step before.  With pose_lr != 0 the cameras of the lost iteration did not move
-                # either (the pose update carries the same guard).
-                if not capacity_error(e):
-                    raise
-                if step > 0:
-                    count_step(-1)
-                    one_iteration(step - 1)
-                    count_step(1)
-                one_iteration(step)
-            if enable_pruning:
-                touch = bool(scene.strategy.is_refine_step(step)) if own_strategy else True
-                if touch:
-                    sh_write_back()
-                scene.strategy.step_post_backward(g, scene.optimizers, scene.strategy_state, step, None, 1e-3)
-                if touch:
-                    sh_c[0] = g["shN"].data[:, :4].contiguous()
-            step += 1
-        if world == 1 and iters > 0:
-            try:   # the last step's count is still in flight: settle it now so that an overflow cannot go unnoticed
-                ops.settle(ctx)
-            except _lib_mod.St3rError as e:
-                if not capacity_error(e):
-                    raise
-                one_iteration(iters - 1)   # its update was skipped on the device: repeat it
-    finally:
-        ops.set_gt_moments(ctx, None, None)
-        if depth_on:
-            ops.set_depth_prior(ctx, None, None, None)
-        if exposure_on:
-            ops.set_exposure(ctx, None, None, None)
-        if intrinsics_on:
-            ops.set_intrinsics_grad(ctx, None, None)
+    try:
+        with _registered(c, options):
+            step = 0
+            for _ in _iterations(iters, verbose):
+                if enable_pruning:
+                    if not own_strategy:
+                        sh_write_back()
+                    scene.strategy.step_pre_backward(g, scene.optimizers, scene.strategy_state, step, None)
+                    if not own_strategy:
+                        sh_c[0] = g["shN"].data[:, :4].contiguous()
+                count_step(1)
+                try:
+                    one_iteration(step)
+                except _lib_mod.St3rError as e:
+                    # ST3R_ERR_CAPACITY is reported by the call AFTER the asynchronous step that outgrew its buffers (> 25 %
+                    # more tile intersections than the step before it).  That step's records past the capacity were dropped
+                    # and its Adam update was skipped on the device (k_adam's guard), so no parameter update has to be
+                    # undone: the lost iteration is repeated -- the context is back on the exactly sized path -- and then
+                    # this one runs.  With enable_pruning the strategy hooks of the lost iteration have already run on the
+                    # un-updated parameters (its position noise, and on a refinement step its relocation / growth): they are
+                    # NOT run again, i.e. the noise of that one iteration is drawn before its update instead of after it.  A
+                    # deviation of one step's noise (tests/test_gpu_api.py::test_run_3dgs_optim_repeats_...); overflows need
+                    # > 25 % more tile intersections than the step before.  With pose_lr != 0 the cameras of the lost
+                    # iteration did not move either (the pose update carries the same guard).
+                    if not capacity_error(e):
+                        raise
+                    if step > 0:
+                        count_step(-1)
+                        one_iteration(step - 1)
+                        count_step(1)
+                    one_iteration(step)
+                if enable_pruning:
+                    touch = bool(scene.strategy.is_refine_step(step)) if own_strategy else True
+                    if touch:
+                        sh_write_back()
+                    scene.strategy.step_post_backward(g, scene.optimizers, scene.strategy_state, step, None, 1e-3)
+                    if touch:
+                        sh_c[0] = g["shN"].data[:, :4].contiguous()
+                step += 1
+            if world == 1 and iters > 0:
+                try:   # the last step's count is still in flight: settle it now so that an overflow cannot go unnoticed
+                    ops.settle(ctx)
+                except _lib_mod.St3rError as e:
+                    if not capacity_error(e):
+                        raise
+                    one_iteration(iters - 1)   # its update was skipped on the device: repeat it
+    finally:   # (behind the clearing of what was registered)
         if sh_c[0].shape[0] == g["shN"].shape[0]:
             sh_write_back()
         if restore_exchange is not None:   # (the moments stay complete on every rank: rs_ag goes on using its own piece)
             ops.set_exchange(ctx, restore_exchange)
-        if poses_on:
-            # a NEW c2w tensor, so that Scene.w2c's cache refreshes itself; inverted in double, device and dtype as before
-            old = scene.c2w
-            c2w = torch.inverse(w2c.double()).to(device=old.device, dtype=old.dtype)
-            if frozen:
-                c2w[frozen] = old.detach()[frozen]
-            scene.c2w = c2w
-        if intrinsics_on:
-            # a NEW intrinsics tensor, device and dtype as before; frozen views keep their rows bit for bit
-            old = scene.intrinsics
-            K_new = Ks.to(device=old.device, dtype=old.dtype)
-            if k_frozen:
-                K_new[k_frozen] = old.detach()[k_frozen]
-            scene.intrinsics = K_new
-    _dist.all_reduce_sum(losses)
-    return losses[:iters].cpu().tolist()   # one device->host copy for the whole call (reference: .item() per step)
+        for o in options:
+            o.finish(c)
+    return _losses_list(losses, iters)
 
 
 def _sharded_layout(scene, world, enable_pruning):
@@ -772,14 +881,9 @@ def _run_3dgs_optim_sharded(scene, iters, ssim_fac, opac_fac, scale_fac, verbose
 
     tr, P, N, n, lo, counts = shard()
     losses = torch.zeros(max(iters, 1), device=scene.device)
-    it_range = range(iters)
-    if verbose:
-        from tqdm import trange
-        it_range = trange(iters)
     strategy, state = scene.strategy, scene.strategy_state
-    try:
-        ops.set_gt_moments(ctx, gt, _gt_moments(scene, ctx, gt))
-        for step in it_range:
+    with _registered(types.SimpleNamespace(scene=scene, ctx=ctx, gt=gt)):
+        for step in _iterations(iters, verbose):
             tr.step(losses[step:step + 1])
             if enable_pruning:   # MCMCStrategy.step_post_backward, shard-wise
                 seed, call = state.get("seed", 0), state.get("calls", 0)
@@ -791,11 +895,8 @@ def _run_3dgs_optim_sharded(scene, iters, ssim_fac, opac_fac, scale_fac, verbose
                         tr, P, N, n, lo, counts = shard()
                     ops.mcmc_noise(ctx, {k: P[k] for k in ("means", "quats", "scales", "opacities")},
                                    1e-3 * strategy.noise_lr, seed, call, row_offset=lo)
-    finally:
-        ops.set_gt_moments(ctx, None, None)
     unshard(tr, P, N, n, counts)
-    _dist.all_reduce_sum(losses)
-    return losses[:iters].cpu().tolist()
+    return _losses_list(losses, iters)
 
 
 train = run_3dgs_optim  # alias for the wording of BASELINE.json's north_star ("gs.train()")

@@ -117,18 +117,14 @@ class Scene:
     def run_3dgs_optim(self, iters: int, enable_pruning: bool = False, loss_ssim_fac=0.2, loss_opacity_fac=0.01,
                        loss_scale_fac=0.01, verbose: bool = False, pose_lr=0.0, pose_freeze=(), depth_fac=0.0,
                        depth_conf_thres=1.5, exposure_lr=0.0, exposure_freeze=()) -> list:
-        poses_off = not callable(pose_lr) and float(pose_lr) == 0.0 and not tuple(pose_freeze)
+        # gs.py gets the reference's call, argument for argument, when the options are off; each option that is on adds its
+        # keywords and those of the options before it
+        kw = {}
         if callable(exposure_lr) or float(exposure_lr) != 0.0:
-            return _gs.run_3dgs_optim(self, iters, enable_pruning, loss_ssim_fac, loss_opacity_fac, loss_scale_fac,
-                                      verbose, pose_lr=pose_lr, pose_freeze=pose_freeze, depth_fac=depth_fac,
-                                      depth_conf_thres=depth_conf_thres, exposure_lr=exposure_lr,
-                                      exposure_freeze=exposure_freeze)
-        if float(depth_fac) != 0.0:
-            return _gs.run_3dgs_optim(self, iters, enable_pruning, loss_ssim_fac, loss_opacity_fac, loss_scale_fac,
-                                      verbose, pose_lr=pose_lr, pose_freeze=pose_freeze, depth_fac=depth_fac,
-                                      depth_conf_thres=depth_conf_thres)
-        if poses_off:   # the reference's call
-            return _gs.run_3dgs_optim(self, iters, enable_pruning, loss_ssim_fac, loss_opacity_fac, loss_scale_fac,
-                                      verbose)
-        return _gs.run_3dgs_optim(self, iters, enable_pruning, loss_ssim_fac, loss_opacity_fac, loss_scale_fac,
-                                  verbose, pose_lr=pose_lr, pose_freeze=pose_freeze)
+            kw = dict(exposure_lr=exposure_lr, exposure_freeze=exposure_freeze)
+        if kw or float(depth_fac) != 0.0:
+            kw = dict(depth_fac=depth_fac, depth_conf_thres=depth_conf_thres, **kw)
+        if kw or callable(pose_lr) or float(pose_lr) != 0.0 or tuple(pose_freeze):
+            kw = dict(pose_lr=pose_lr, pose_freeze=pose_freeze, **kw)
+        return _gs.run_3dgs_optim(self, iters, enable_pruning, loss_ssim_fac, loss_opacity_fac, loss_scale_fac, verbose,
+                                  **kw)

@@ -18,7 +18,7 @@ from oracle import gs_oracle as go
 from oracle import gs_torch_ref as tr
 from st3r_synth import synth
 from test_gpu_gs import FUZZ_CHECKED
-from test_gpu_pose_grad import _gen, _pose_errors, _se3_exp, dev, make, rel_err_per_camera, run_hip
+from per_view_cases import _gen, _pose_errors, _se3_exp, dev, make, rel_err_per_camera, run_hip
 
 NAMED = ["small", "ragged", "medium", "one", "many", "wide"]
 FUZZ3 = ["fuzz0", "fuzz1", "fuzz2"]

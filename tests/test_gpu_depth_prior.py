@@ -18,8 +18,8 @@ pytestmark = pytest.mark.gpu
 from oracle import gs_oracle as go
 from st3r_synth import synth
 from test_gpu_depth import render_dense_depth   # (the arithmetic dense_loss_grads restates band by band)
-from test_gpu_pose_grad import dev, make, rel_err_per_camera
-from test_gpu_pose_train import B1, B2, EPS, _Run, _medium, _optim_scene, _same_bits, _setup
+from per_view_cases import (B1, B2, EPS, _Run, _medium, _optim_scene, _same_bits, _setup, _small_scene,
+                            _synthetic_prior, dev, make, rel_err_per_camera)
 
 BLOCKS = ("means", "quats", "scales", "opacities", "sh")
 DEPTH_FAC = 0.5
@@ -143,24 +143,6 @@ def test_loss_kernel_on_unaligned_buffers(ctx):
 # ---------------------------------------------------------------------------------------------------------------------
 # helpers of the fused-step tests
 # ---------------------------------------------------------------------------------------------------------------------
-def _synthetic_prior(ctx, P, vm, K, W, H, margin=None, seed=4):
-    """the expected depth of the scene's own render, perturbed (5 % relative, 0.02 absolute), and a 0/1 weight map with
-    holes: a third of the pixels at random, every pixel the render hardly reaches (alpha <= 0.05: the quotient ED amplifies
-    float32 noise there) and, when given, the pixels whose blend decisions float32 does not determine"""
-    from starst3r_amd import ops
-    rgb, alpha, info = ops.rasterization(ctx, P["means"], P["quats"], P["scales"], P["opacities"], P["shN"], vm, K, W, H)
-    d = ops.blend_depth_fwd(ctx, info["_splats"], info["isect_offsets"], info["_flatten_ids_dense"], alpha,
-                            info["_last_ids"], vm.shape[0], W, H)
-    ed = (d / alpha.clamp(min=1e-10))[..., 0]
-    gen = torch.Generator(device="cuda:0").manual_seed(seed)
-    Z = ed * (1 + 0.05 * torch.randn(ed.shape, device="cuda:0", generator=gen)) + \
-        0.02 * torch.randn(ed.shape, device="cuda:0", generator=gen)
-    w = (alpha[..., 0] > 0.05) & (torch.rand(ed.shape, device="cuda:0", generator=gen) > 0.33)
-    if margin is not None:
-        w &= torch.tensor(margin > 1e-4, device="cuda:0").reshape(w.shape)
-    return Z.contiguous(), w.float().contiguous(), info
-
-
 def _rel(a, b):
     return float((a.double().cpu() - b.double().cpu()).abs().max() / (b.double().cpu().abs().max() + 1e-30))
 
@@ -613,14 +595,6 @@ def test_add_images_keeps_the_depth_maps(monkeypatch):
     p = pts[0].cpu()
     zc = (p @ w2c[0, :3, :3].T + w2c[0, :3, 3])[:, 2].reshape(96, 128)
     np.testing.assert_allclose(zc.numpy(), scene.depth_maps[0].numpy(), rtol=1e-4, atol=1e-5)
-
-
-def _small_scene():
-    g, w2c, Ks, W, H = make("small")
-    imgs = np.zeros((w2c.shape[0], H, W, 3), np.float32)
-    scene = _optim_scene(g, torch.tensor(w2c), Ks, imgs)
-    scene.depth_maps = [torch.full((H, W), 3.0) for _ in range(w2c.shape[0])]
-    return scene, W, H
 
 
 def test_defaults_reach_the_loop_with_the_reference_arguments(monkeypatch):

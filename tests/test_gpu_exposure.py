@@ -16,8 +16,8 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from st3r_synth import synth
-from test_gpu_pose_grad import dev, make
-from test_gpu_pose_train import B1, B2, EPS, _Run, _medium, _optim_scene, _same_bits, _setup, _ulp_bound
+from per_view_cases import (B1, B2, EPS, _Run, _medium, _optim_scene, _same_bits, _setup, _small_scene, _ulp_bound, dev,
+                            make)
 
 U24, U52 = 2.0 ** -24, 2.0 ** -52
 
@@ -598,14 +598,8 @@ def test_render_3dgs_back_propagates_through_the_exposures(ctx):
 # ---------------------------------------------------------------------------------------------------------------------
 # 10. layouts without exposure training say so
 # ---------------------------------------------------------------------------------------------------------------------
-def _small_scene():
-    g, w2c, Ks, W, H = make("small")
-    imgs = np.zeros((w2c.shape[0], H, W, 3), np.float32)
-    return _optim_scene(g, torch.tensor(w2c), Ks, imgs)
-
-
 def test_exposure_lr_under_the_gaussian_sharded_setting_is_refused(monkeypatch):
-    scene = _small_scene()
+    scene, _, _ = _small_scene(depth=None)
     monkeypatch.setenv("ST3R_MULTI_GPU", "gaussian-sharded")
     with pytest.raises(NotImplementedError):
         scene.run_3dgs_optim(1, exposure_lr=1e-3)
@@ -616,7 +610,7 @@ def test_exposure_lr_under_the_gaussian_sharded_setting_is_refused(monkeypatch):
 
 def test_exposure_lr_under_torch_distributed_is_refused(monkeypatch):
     from starst3r_amd import dist as sdist
-    scene = _small_scene()
+    scene, _, _ = _small_scene(depth=None)
     monkeypatch.setattr(sdist, "rank_world", lambda: (0, 2))
     with pytest.raises(NotImplementedError):
         scene.run_3dgs_optim(1, exposure_lr=1e-3)

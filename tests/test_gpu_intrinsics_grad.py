@@ -17,6 +17,7 @@ pytestmark = pytest.mark.gpu
 from oracle import gs_oracle as go
 from oracle import gs_torch_ref as tr
 from st3r_synth import synth
+from per_view_cases import _gen, dev, make, masked_cotangents, rel_err_per_camera, run_hip
 
 
 @pytest.fixture(scope="module")
@@ -24,45 +25,6 @@ def ctx():
     from starst3r_amd import ops
     assert torch.cuda.is_available(), "GPU tests need a GPU"
     return ops.get_context("cuda:0")
-
-
-def dev(a, dtype=torch.float32):
-    return torch.tensor(np.ascontiguousarray(a), dtype=dtype, device="cuda:0")
-
-
-# the scenes of tests/test_gpu_pose_grad.py
-SCENES = {
-    # name: (N, views, W, H, seed, scale_lo, scale_hi)
-    "small": (400, 3, 96, 64, 7, 0.01, 0.08),
-    "ragged": (1500, 2, 101, 75, 21, 0.01, 0.12),
-    "medium": (20000, 4, 320, 240, 5, 0.004, 0.03),
-    "one": (1, 1, 48, 32, 1, 0.05, 0.06),
-    "many": (800, 9, 64, 48, 3, 0.01, 0.08),
-    "wide": (2500, 3, 320, 240, 13, 0.08, 0.25),
-    # the reduction's edges: one block; one block and a lone Gaussian in a second one
-    "n256": (256, 2, 64, 48, 31, 0.01, 0.08),
-    "n257": (257, 2, 64, 48, 32, 0.01, 0.08),
-}
-
-
-def fuzz_scene(seed):
-    rng = np.random.default_rng(1000 + seed)
-    N = int(rng.integers(200, 1200)); V = int(rng.integers(1, 5))
-    W = int(rng.integers(40, 200)); H = int(rng.integers(30, 150))
-    g, w2c, Ks = synth.make_scene(N, V, W, H, seed=seed, scale_lo=1e-3, scale_hi=0.5)
-    g["means"] = rng.uniform(-3.6, 3.6, (N, 3)).astype(np.float32)
-    g["opacities"] = rng.uniform(-0.3, 1.6, N).astype(np.float32)
-    g["scales"] = (g["scales"] * rng.uniform(0.2, 5.0, (N, 3))).astype(np.float32)
-    g["quats"] = (g["quats"] * rng.uniform(0.1, 3.0, (N, 1))).astype(np.float32)
-    return g, w2c, Ks, W, H
-
-
-def make(name):
-    if name.startswith("fuzz"):
-        return fuzz_scene(int(name[4:]))
-    N, V, W, H, seed, lo, hi = SCENES[name]
-    g, w2c, Ks = synth.make_scene(N, V, W, H, seed=seed, scale_lo=lo, scale_hi=hi)
-    return g, w2c, Ks, W, H
 
 
 def clamp_scene():
@@ -81,27 +43,6 @@ def clamp_scene():
     g = dict(means=means, scales=scales, quats=q.astype(np.float32), opacities=np.full(8, 0.9, np.float32),
              sh0=np.zeros((8, 1, 3), np.float32), shN=sh)
     return g, w2c, Ks, W, H
-
-
-def run_hip(ctx, g, w2c, Ks, W, H):
-    from starst3r_amd import ops
-    P = {k: dev(v) for k, v in g.items()}
-    rgb, alpha, info = ops.rasterization(ctx, P["means"], P["quats"], P["scales"], P["opacities"], P["shN"], dev(w2c),
-                                         dev(Ks), W, H)
-    return P, rgb, alpha, info
-
-
-def masked_cotangents(g, w2c, Ks, W, H, seed=3):
-    """random v_rgb / v_alpha, zero on the pixels whose skip / stop decisions float32 does not determine (as
-    test_gpu_gs.test_backward_vs_oracle)"""
-    rgb_o, alpha_o, meta = go.rasterization(g["means"], g["quats"], g["scales"], g["opacities"], g["shN"], w2c, Ks,
-                                            W, H, want_margin=True)
-    rng = np.random.default_rng(seed)
-    v_rgb = rng.standard_normal(rgb_o.shape).astype(np.float32)
-    v_alpha = rng.standard_normal(alpha_o.shape).astype(np.float32)
-    und = ~(meta["margin"] > 1e-4)
-    v_rgb[und] = 0.0; v_alpha[und] = 0.0
-    return v_rgb, v_alpha
 
 
 def pair_grads(ctx, P, rgb, alpha, info, w2c, Ks, W, H, v_rgb, v_alpha):
@@ -150,14 +91,6 @@ def scaled(v4, Ks, W, H):
     K = torch.as_tensor(Ks).double().cpu()
     s = torch.stack([K[:, 0, 0], K[:, 1, 1], torch.full_like(K[:, 0, 0], float(W)), torch.full_like(K[:, 0, 0], float(H))], -1)
     return v4.detach().double().cpu() * s
-
-
-def rel_err_per_camera(a, b):
-    return [float((a[c] - b[c]).abs().max() / (b[c].abs().max() + 1e-30)) for c in range(b.shape[0])]
-
-
-def _gen(seed):
-    return torch.Generator(device="cuda:0").manual_seed(seed)
 
 
 FUZZ3 = ["fuzz0", "fuzz1", "fuzz2"]

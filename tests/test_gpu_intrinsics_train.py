@@ -15,37 +15,9 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from st3r_synth import synth
+from per_view_cases import (B1, B2, EPS, _Run, _medium, _optim_scene, _same_bits, _setup, _synthetic_prior, dev, make)
 
-B1, B2, EPS = 0.9, 0.999, 1e-8
 DEPTH_FAC = 0.5
-
-
-def dev(a, dtype=torch.float32):
-    return torch.tensor(np.ascontiguousarray(a), dtype=dtype, device="cuda:0")
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32)
-
-
-def _same_bits(a, b):
-    return torch.equal(_bits(a), _bits(b))
-
-
-# the scenes of tests/test_gpu_pose_grad.py
-SCENES = {
-    # name: (N, views, W, H, seed, scale_lo, scale_hi)
-    "small": (400, 3, 96, 64, 7, 0.01, 0.08),
-    "ragged": (1500, 2, 101, 75, 21, 0.01, 0.12),
-    "many": (800, 9, 64, 48, 3, 0.01, 0.08),
-    "wide": (2500, 3, 320, 240, 13, 0.08, 0.25),
-}
-
-
-def make(name):
-    N, V, W, H, seed, lo, hi = SCENES[name]
-    g, w2c, Ks = synth.make_scene(N, V, W, H, seed=seed, scale_lo=lo, scale_hi=hi)
-    return g, w2c, Ks, W, H
 
 
 @pytest.fixture(scope="module")
@@ -196,43 +168,10 @@ def test_bad_intrinsics_step_is_refused(ctx):
 # ---------------------------------------------------------------------------------------------------------------------
 # helpers of the fused-step tests
 # ---------------------------------------------------------------------------------------------------------------------
-def _setup(ctx, g, w2c, Ks, W, H, noise_seed=1):
-    """device parameters, cameras and a noisy ground truth of the scene's own render"""
-    from starst3r_amd import ops
-    P = {k: dev(v) for k, v in g.items()}
-    vm, K = dev(w2c), dev(Ks)
-    campos = ops.camera_positions(vm)
-    rgb, _, _ = ops.render(ctx, P, vm, K, campos, W, H)
-    gen = torch.Generator(device="cuda:0").manual_seed(noise_seed)
-    gt = torch.clamp(rgb + 0.05 * torch.randn(rgb.shape, device="cuda:0", generator=gen), 0, 1).contiguous()
-    return P, vm, K, campos, gt
-
-
-def _medium(ctx):
-    N, V, W, H = 20000, 3, 320, 240
-    g, w2c, Ks = synth.make_scene(N, V, W, H, seed=5, scale_lo=0.004, scale_hi=0.03)
-    return _setup(ctx, g, w2c, Ks, W, H) + (W, H)
-
-
 def _exposures(C, seed):
     gen = torch.Generator().manual_seed(seed)
     E = torch.eye(3, 4).repeat(C, 1, 1) + 0.1 * torch.randn((C, 3, 4), generator=gen)
     return E.contiguous()
-
-
-def _synthetic_prior(ctx, P, vm, K, W, H, seed=4):
-    """the expected depth of the scene's own render, perturbed, and a 0/1 weight map with holes (as
-    tests/test_gpu_depth_prior.py)"""
-    from starst3r_amd import ops
-    rgb, alpha, info = ops.rasterization(ctx, P["means"], P["quats"], P["scales"], P["opacities"], P["shN"], vm, K, W, H)
-    d = ops.blend_depth_fwd(ctx, info["_splats"], info["isect_offsets"], info["_flatten_ids_dense"], alpha,
-                            info["_last_ids"], vm.shape[0], W, H)
-    ed = (d / alpha.clamp(min=1e-10))[..., 0]
-    gen = torch.Generator(device="cuda:0").manual_seed(seed)
-    Z = ed * (1 + 0.05 * torch.randn(ed.shape, device="cuda:0", generator=gen)) + \
-        0.02 * torch.randn(ed.shape, device="cuda:0", generator=gen)
-    w = (alpha[..., 0] > 0.05) & (torch.rand(ed.shape, device="cuda:0", generator=gen) > 0.33)
-    return Z.contiguous(), w.float().contiguous()
 
 
 def _unfused(ctx, P, vm, K, gt, W, H, ssim_fac=0.2, E=None, prior=None):
@@ -258,27 +197,6 @@ def _unfused(ctx, P, vm, K, gt, W, H, ssim_fac=0.2, E=None, prior=None):
     vvm = ops.viewmat_bwd(ctx, P["means"], P["quats"], P["scales"], P["shN"], vm, K, info["_campos"], W, H, info["_splats"], vs)
     torch.cuda.synchronize()
     return vK, vvm
-
-
-class _Run:
-    """the tensors of a training run through ops.train_step / ops.train_step_poses with trained intrinsics"""
-
-    def __init__(self, P0, vm, campos, K, steps):
-        N, Cn = P0["means"].shape[0], vm.shape[0]
-        self.P = {k: v.clone() for k, v in P0.items()}
-        self.vm, self.campos, self.K = vm.clone(), campos.clone(), K.clone()
-        self.grads = torch.empty(23 * N, device="cuda:0")
-        self.m = torch.zeros_like(self.grads); self.v = torch.zeros_like(self.grads)
-        self.pm = torch.zeros(6 * Cn, device="cuda:0"); self.pv = torch.zeros_like(self.pm)
-        self.km = torch.zeros(4 * Cn, device="cuda:0"); self.kv = torch.zeros_like(self.km)
-        self.losses = torch.zeros(steps, device="cuda:0")
-        self.vvm = torch.zeros((Cn, 4, 4), device="cuda:0")
-        self.vK = torch.full((Cn, 4), 7.0, device="cuda:0")
-        self.snaps = []
-
-    def state(self):
-        return [self.P[k] for k in sorted(self.P)] + [self.m, self.v, self.vm, self.campos, self.pm, self.pv, self.K, self.km,
-                                                      self.kv, self.losses]
 
 
 def _step(ctx, r, gt, W, H, it, poses=False, k_lr=1e-3, mask=None, want_stats=True, adam=True):
@@ -358,11 +276,11 @@ def test_registration_combines_with_poses_depth_prior_and_exposures():
     P, vm, K, campos, gt = _setup(ctx, g, w2c, Ks, W, H)
     Cn = vm.shape[0]
     E = _exposures(Cn, 77).cuda()
-    prior = _synthetic_prior(ctx, P, vm, K, W, H)
+    prior = _synthetic_prior(ctx, P, vm, K, W, H)[:2]
     plain, plain_vm = _unfused(ctx, P, vm, K, gt, W, H)
 
     def fused(poses, with_E, with_prior, register=True):
-        r = _Run(P, vm, campos, K, 1)
+        r = _Run(P, vm, campos, 1, K)
         vE = torch.zeros_like(E)
         if with_E:
             ops.set_exposure(ctx, gt, E, vE)
@@ -403,16 +321,16 @@ def test_cleared_registration_changes_nothing():
     ctx = ops.Context("cuda:0")
     P0, vm, K, campos, gt, W, H = _medium(ctx)
     steps = 3
-    a = _Run(P0, vm, campos, K, steps)
+    a = _Run(P0, vm, campos, steps, K)
     for it in range(steps):
         _step(ctx, a, gt, W, H, it, adam=False)
-    b = _Run(P0, vm, campos, K, steps)
+    b = _Run(P0, vm, campos, steps, K)
     ops.set_intrinsics_grad(ctx, gt, b.vK)
     ops.set_intrinsics_grad(ctx, None, None)
     for it in range(steps):
         _step(ctx, b, gt, W, H, it, adam=False)
     # registered, with every view masked: the gradient is written, nothing moves
-    c = _Run(P0, vm, campos, K, steps)
+    c = _Run(P0, vm, campos, steps, K)
     ops.set_intrinsics_grad(ctx, gt, c.vK)
     mask = torch.zeros(vm.shape[0], device="cuda:0")
     for it in range(steps):
@@ -435,7 +353,7 @@ def test_async_intrinsics_steps_equal_synchronous_steps():
     for want_stats in (True, False):
         ctx = ops.Context("cuda:0")   # a private context: the record-count hint is per context
         P0, vm, K, campos, gt, W, H = _medium(ctx)
-        r = _Run(P0, vm, campos, K, steps)
+        r = _Run(P0, vm, campos, steps, K)
         ops.set_intrinsics_grad(ctx, gt, r.vK)
         for it in range(steps):
             _step(ctx, r, gt, W, H, it, poses=True, want_stats=want_stats)
@@ -457,7 +375,7 @@ def test_overflowing_async_intrinsics_step_moves_nothing_and_is_repeated():
     def steps(overflow_at):
         ctx = ops.Context("cuda:0")
         P0, vm, K, campos, gt, W, H = _medium(ctx)
-        r = _Run(P0, vm, campos, K, 3)
+        r = _Run(P0, vm, campos, 3, K)
         ops.set_intrinsics_grad(ctx, gt, r.vK)
         it = 0
         while it < 3:
@@ -490,7 +408,7 @@ def test_intrinsics_gradient_with_a_communicator_is_invalid():
     ctx = ops.Context("cuda:0")
     g, w2c, Ks, W, H = make("small")
     P0, vm, K, campos, gt = _setup(ctx, g, w2c, Ks, W, H)
-    r = _Run(P0, vm, campos, K, 1)
+    r = _Run(P0, vm, campos, 1, K)
     r.grads.fill_(7.0)
     before = [x.clone() for x in r.state() + [r.grads, r.vK]]
     sdist.attach_native_comm(ctx)
@@ -518,22 +436,6 @@ OPTIM_LR = 2e-3
 
 def _optim_lr(step):
     return 0.1 * OPTIM_LR + 0.9 * OPTIM_LR * (1 + math.cos(math.pi * step / OPTIM_ITERS)) / 2   # a cosine 2e-3 -> 2e-4
-
-
-def _optim_scene(g_start, w2c, Ks_start, imgs):
-    import starst3r_amd as st
-    from starst3r_amd import gs
-    scene = st.Scene(device="cuda:0")
-    scene.imgs = [imgs[i] for i in range(imgs.shape[0])]
-    scene.c2w = torch.inverse(torch.tensor(w2c).double()).float()   # CPU float32 tensors, as the reconstruction leaves them
-    scene.intrinsics = torch.tensor(Ks_start)
-    scene.gaussians = {k: torch.nn.Parameter(dev(v)) for k, v in g_start.items()}
-    scene._gs_optim = gs._OptimState(scene, 1e-3)
-    scene.optimizers = {k: gs.FusedAdam(scene._gs_optim, k) for k in scene.gaussians}
-    scene.strategy = gs.MCMCStrategy()
-    scene.strategy_state = scene.strategy.initialize_state()
-    scene._gt_dev = None
-    return scene
 
 
 def test_focal_refinement_through_run_3dgs_optim(ctx):

@@ -15,17 +15,8 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from st3r_synth import synth
-from test_gpu_pose_grad import _pose_errors, _se3_exp, dev, make, rel_err_per_camera
-
-B1, B2, EPS = 0.9, 0.999, 1e-8
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32)
-
-
-def _same_bits(a, b):
-    return torch.equal(_bits(a), _bits(b))
+from per_view_cases import (B1, B2, EPS, _Run, _medium, _optim_scene, _pose_errors, _same_bits, _se3_exp, _setup,
+                            _ulp_bound, dev, make, rel_err_per_camera)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -69,12 +60,6 @@ def _random_rigid(C, gen):
     V = torch.zeros((C, 4, 4), dtype=torch.float64)
     V[:, :3, :3] = R; V[:, :3, 3] = 3.0 * torch.randn((C, 3), dtype=torch.float64, generator=gen); V[:, 3, 3] = 1.0
     return V
-
-
-def _ulp_bound(ref, n_ulp=2):
-    """n_ulp float32 ulps of the largest entry magnitude, per camera"""
-    big = ref.reshape(ref.shape[0], -1).abs().max(dim=1).values.float().numpy()
-    return n_ulp * np.spacing(big).astype(np.float64)
 
 
 def _run_kernel_steps(ctx, C, steps, lr, use_mask, check):
@@ -148,18 +133,6 @@ def test_pose_adam_kernel_vs_fp64(ctx, C):
 # ---------------------------------------------------------------------------------------------------------------------
 # helpers of the fused-step tests
 # ---------------------------------------------------------------------------------------------------------------------
-def _setup(ctx, g, w2c, Ks, W, H, noise_seed=1):
-    """device parameters, cameras and a noisy ground truth of the scene's own render"""
-    from starst3r_amd import ops
-    P = {k: dev(v) for k, v in g.items()}
-    vm, K = dev(w2c), dev(Ks)
-    campos = ops.camera_positions(vm)
-    rgb, _, _ = ops.render(ctx, P, vm, K, campos, W, H)
-    gen = torch.Generator(device="cuda:0").manual_seed(noise_seed)
-    gt = torch.clamp(rgb + 0.05 * torch.randn(rgb.shape, device="cuda:0", generator=gen), 0, 1).contiguous()
-    return P, vm, K, campos, gt
-
-
 def _unfused_pose_grad(ctx, P, vm, K, gt, W, H, ssim_fac):
     from starst3r_amd import ops
     Cn = vm.shape[0]
@@ -171,24 +144,6 @@ def _unfused_pose_grad(ctx, P, vm, K, gt, W, H, ssim_fac):
                           info["_splats"], v_splats)
     torch.cuda.synchronize()
     return out
-
-
-class _Run:
-    """the tensors of a training run through ops.train_step / ops.train_step_poses"""
-
-    def __init__(self, P0, vm, campos, steps):
-        N, Cn = P0["means"].shape[0], vm.shape[0]
-        self.P = {k: v.clone() for k, v in P0.items()}
-        self.vm, self.campos = vm.clone(), campos.clone()
-        self.grads = torch.empty(23 * N, device="cuda:0")
-        self.m = torch.zeros_like(self.grads); self.v = torch.zeros_like(self.grads)
-        self.pm = torch.zeros(6 * Cn, device="cuda:0"); self.pv = torch.zeros_like(self.pm)
-        self.losses = torch.zeros(steps, device="cuda:0")
-        self.vvm = torch.zeros((Cn, 4, 4), device="cuda:0")
-        self.snaps = []
-
-    def state(self):
-        return [self.P[k] for k in sorted(self.P)] + [self.m, self.v, self.vm, self.campos, self.pm, self.pv, self.losses]
 
 
 def _step_poses(ctx, r, K, gt, W, H, it, lr=1e-3, pose_lr=1e-3, mask=None, want_stats=True, ssim_fac=0.2, reg=0.01):
@@ -223,12 +178,6 @@ def test_fused_pose_gradient_equals_unfused_chain(name):
 # ---------------------------------------------------------------------------------------------------------------------
 # 3. nothing else moves
 # ---------------------------------------------------------------------------------------------------------------------
-def _medium(ctx):
-    N, V, W, H = 20000, 3, 320, 240
-    g, w2c, Ks = synth.make_scene(N, V, W, H, seed=5, scale_lo=0.004, scale_hi=0.03)
-    return _setup(ctx, g, w2c, Ks, W, H) + (W, H)
-
-
 def test_masked_poses_change_nothing():
     from starst3r_amd import ops
     ctx = ops.Context("cuda:0")
@@ -443,22 +392,6 @@ JOINT_LR = 2e-3   # a cosine from JOINT_LR to JOINT_LR / 10: the rates of test_p
 
 def _joint_pose_lr(step):
     return 0.1 * JOINT_LR + 0.9 * JOINT_LR * (1 + math.cos(math.pi * step / JOINT_ITERS)) / 2
-
-
-def _optim_scene(g_start, w2c_start, Ks, imgs):
-    import starst3r_amd as st
-    from starst3r_amd import gs
-    scene = st.Scene(device="cuda:0")
-    scene.imgs = [imgs[i] for i in range(imgs.shape[0])]
-    scene.c2w = torch.inverse(w2c_start.double()).float()   # a CPU float32 tensor, as the reconstruction leaves it
-    scene.intrinsics = torch.tensor(Ks)
-    scene.gaussians = {k: torch.nn.Parameter(dev(v)) for k, v in g_start.items()}
-    scene._gs_optim = gs._OptimState(scene, 1e-3)
-    scene.optimizers = {k: gs.FusedAdam(scene._gs_optim, k) for k in scene.gaussians}
-    scene.strategy = gs.MCMCStrategy()
-    scene.strategy_state = scene.strategy.initialize_state()
-    scene._gt_dev = None
-    return scene
 
 
 def test_joint_refinement_through_run_3dgs_optim(ctx):

@@ -15,8 +15,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from st3r_synth import synth
-from test_gpu_depth_prior import _small_scene, _synthetic_prior
-from test_gpu_pose_train import _same_bits, _setup
+from per_view_cases import _same_bits, _setup, _small_scene, _synthetic_prior
 
 N, V, W, H = 300, 3, 40, 24   # 3 x 2 tiles with ragged edges; H even: the images can be viewed as (V, H / 2, 2 W, 3)
 
