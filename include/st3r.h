@@ -224,6 +224,35 @@ int st3r_loss_l1_ssim(st3r_ctx* ctx, void* stream, int C, int height, int width,
 int st3r_loss_gt_moments(st3r_ctx* ctx, void* stream, int C, int height, int width, const float* gt, float* moments);
 int st3r_ctx_set_gt_moments(st3r_ctx* ctx, const float* gt, const float* moments, int C, int height, int width);
 
+/* L1 + SSIM of C views under per-pixel weights: weight [C,H,W] float32, >= 0 and finite -- 0 drops the pixel, 1 is the
+ * plain loss, anything else is allowed (a confidence).  With I the SSIM interior (rows 5 .. H-6, columns 5 .. W-6; empty
+ * when H <= 10 or W <= 10) and ssim(p,ch) the map of st3r_loss_l1_ssim:
+ *   n1 = max(sum_p w, 1)        n2 = max(sum_{p in I} w, 1)
+ *   loss_c = w_l1 sum_p w sum_ch |gt - r| / (3 n1) + w_ssim sum_{p in I} w sum_ch (1 - ssim(p,ch)) / (3 n2)
+ * The weight multiplies the SSIM map at the window's CENTRE; the 11 x 11 windows themselves stay unweighted, so a pixel
+ * within 5 px (Chebyshev distance) of a pixel with w > 0 still enters that pixel's window.  A pixel with w == 0
+ * contributes exact zeros to the sums and to the derivative maps whatever finite values gt holds around it; a view whose
+ * weights are all zero contributes 0 and gets an all-zero gradient.  With w == 1 everywhere the first two sums and
+ * v_render are the bits of st3r_loss_l1_ssim.
+ * sums [C,4] (double, device; written): per view  sum_p w sum_ch |gt - r|,  sum_{p in I} w sum_ch ssim,  n1,  n2 (in double,
+ * in a fixed order, no atomics).  v_render [C,H,W,3] = d(sum_c loss_c)/d render; may be NULL.  Nothing is differentiated
+ * with respect to the weights.  Registered ground-truth moments (st3r_ctx_set_gt_moments) are used as by st3r_loss_l1_ssim. */
+int st3r_loss_l1_ssim_weighted(st3r_ctx* ctx, void* stream, int C, int height, int width, const float* render,
+                               const float* gt, const float* weight, float w_l1, float w_ssim, double* sums,
+                               float* v_render);
+
+/* Registers the per-pixel loss weights [C,H,W] of the images at `gt` [C,H,W,3].  From then on st3r_gs_train_fwd_bwd /
+ * _step / _step_poses take the weighted loss above (w_l1 = 1 - ssim_fac, w_ssim = ssim_fac) whenever their ground-truth
+ * pointer is `gt` or a whole-view offset into it (view chunks) with the same height and width; loss_out is the weighted
+ * loss.  The sums of the weights are computed once per registration, by the first call that uses it and on that call's
+ * stream (the rule of st3r_ctx_set_depth_prior).  With exposures registered the weighted loss is taken on y = E x, and
+ * st3r_exposure_bwd sees the weighted d loss / d y; the depth prior (which keeps its own weights), the pose gradient, the
+ * intrinsics gradient and the registered ground-truth moments are unchanged and combine with it.  With no registration
+ * every call runs exactly the launches it ran before.  The buffer stays the CALLER's and must stay unchanged while
+ * registered; gt = NULL or weight = NULL clears the registration.  st3r_gs_raster_train ignores it; with a communicator
+ * attached the training calls return ST3R_ERR_INVALID while a registration applies. */
+int st3r_ctx_set_loss_weight(st3r_ctx* ctx, const float* gt, const float* weight, int C, int height, int width);
+
 /* Depth-prior loss of C views: a weighted L1 between the expected depth of a render and a per-pixel prior.
  * depth, alpha [C,H,W,1]: D and alpha of the render (st3r_gs_blend_depth_fwd, st3r_gs_blend_fwd); prior, weight [C,H,W],
  * weight >= 0.

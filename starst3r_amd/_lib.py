@@ -46,6 +46,8 @@ SIGNATURES = {
     "st3r_loss_l1_ssim": [vp, vp, i32, i32, i32, vp, vp, f32, f32, vp, vp],
     "st3r_loss_gt_moments": [vp, vp, i32, i32, i32, vp, vp],
     "st3r_ctx_set_gt_moments": [vp, vp, vp, i32, i32, i32],
+    "st3r_loss_l1_ssim_weighted": [vp, vp, i32, i32, i32, vp, vp, vp, f32, f32, vp, vp],
+    "st3r_ctx_set_loss_weight": [vp, vp, vp, i32, i32, i32],
     "st3r_loss_depth_prior": [vp, vp, i32, i32, i32, vp, vp, vp, vp, f32, vp, vp, vp],
     "st3r_ctx_set_depth_prior": [vp, vp, vp, vp, i32, i32, i32, f32],
     "st3r_exposure_fwd": [vp, vp, i32, i32, i32, vp, vp, vp],

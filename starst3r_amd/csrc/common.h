@@ -90,6 +90,8 @@ enum ArenaSlot {
     SLOT_SCAN_CHAIN_B, // the band-counter scan of the banded emission (gs_isect.hip): a control block of its own, so that no clear of it can touch the pair-order scan's total while the step still reads it
     SLOT_EXPOSED,     // fused step with exposures (fused_step.hip): the exposed image y [C,H,W,3] the loss reads (SLOT_RGB keeps the raw render)
     SLOT_KGRAD_PART,  // intrinsics backward (gs_intrinsics.hip): one 4-double partial per (camera, block of 256 Gaussians)
+    SLOT_LWEIGHT_PART, // per-pixel loss weights (loss.hip): one 2-double partial per (view, workgroup) of their sums
+    SLOT_LWEIGHT_NORM, // the same: (sum_p w, sum_{p in I} w) of every registered view, computed once per registration
     SLOT_COUNT
 };
 
@@ -165,6 +167,9 @@ struct st3r_ctx {
     ViewReg ex; const float* ex_exposure; float* ex_v_exposure;
     // intrinsics gradient (st3r_ctx_set_intrinsics_grad, gs_intrinsics.hip): where d loss / d (fx, fy, cx, cy) goes
     ViewReg kg; float* kg_v_Ks;
+    // per-pixel loss weights (st3r_ctx_set_loss_weight, loss.hip); lw_norm_valid: SLOT_LWEIGHT_NORM holds the sums of this
+    // registration (computed by the first training call that uses it)
+    ViewReg lw; const float* lw_weight; int lw_norm_valid;
     int bwd_stamp;  // generation stamp of the per-(record, tile) partial-gradient slots
     int depth_stamp;  // the same for the depth backward's slots (SLOT_VTILE_DEPTH)
     uint32_t scan_gen;   // single-pass scan (gs_isect.hip): generation of its status words

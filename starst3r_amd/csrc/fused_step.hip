@@ -221,10 +221,16 @@ static int rasterize_front(st3r_ctx* ctx, hipStream_t s, const GsParams& g, cons
 __global__ void k_finalize_loss(int C, const double* __restrict__ sums, const double* __restrict__ reg_sums,
                                 double inv_px, double inv_cnt, double w_l1, double w_ssim, double reg_views,
                                 double opac_k, double scale_k, float* __restrict__ loss_out,
-                                const double* __restrict__ dsums, const double* __restrict__ dnorm, double depth_fac) {
+                                const double* __restrict__ dsums, const double* __restrict__ dnorm, double depth_fac,
+                                const double* __restrict__ wnorm) {
     if (threadIdx.x == 0 && blockIdx.x == 0) {
         double loss = 0;
-        for (int c = 0; c < C; ++c) loss += w_l1 * sums[2 * c] * inv_px + w_ssim * (1.0 - sums[2 * c + 1] * inv_cnt);
+        if (wnorm)   // per-pixel weights (loss.hip): wnorm[2c], wnorm[2c + 1] = sum_p w, sum_{p in I} w of view c
+            for (int c = 0; c < C; ++c)
+                loss += w_l1 * sums[2 * c] / (3.0 * fmax(wnorm[2 * c], 1.0)) +
+                        w_ssim * (3.0 * wnorm[2 * c + 1] - sums[2 * c + 1]) / (3.0 * fmax(wnorm[2 * c + 1], 1.0));
+        else
+            for (int c = 0; c < C; ++c) loss += w_l1 * sums[2 * c] * inv_px + w_ssim * (1.0 - sums[2 * c + 1] * inv_cnt);
         loss += reg_views * (opac_k * reg_sums[0] + scale_k * reg_sums[1]);
         if (dsums)   // depth prior (loss_depth.hip): depth_fac sum_p w |ED - Z| / n_c per view
             for (int c = 0; c < C; ++c) loss += depth_fac * dsums[c] / dnorm[c];
@@ -232,15 +238,16 @@ __global__ void k_finalize_loss(int C, const double* __restrict__ sums, const do
     }
 }
 
-// the per-view sums of a step -> its loss; dp_sums == NULL: no depth term
+// the per-view sums of a step -> its loss; dp_sums == NULL: no depth term; lw.weight != NULL: the weighted loss, normalised
+// by the sums of the views' weights
 static int finalize_loss(hipStream_t s, int C, int H, int W, const double* sums, const double* reg_sums, float ssim_fac,
                          double reg_views, double opac_k, double scale_k, float* loss_out, const double* dp_sums,
-                         const DepthPrior& dp) {
+                         const DepthPrior& dp, const LossWeight& lw) {
     const int Hi = H - 10, Wi = W - 10;
     const double cnt = (Hi > 0 && Wi > 0) ? (double)Hi * Wi * 3 : 0.0;
     hipLaunchKernelGGL(k_finalize_loss, dim3(1), dim3(64), 0, s, C, sums, reg_sums, 1.0 / ((double)H * W * 3),
                        cnt > 0 ? 1.0 / cnt : 0.0, (double)(1.0f - ssim_fac), (double)ssim_fac, reg_views, opac_k, scale_k,
-                       loss_out, dp_sums, dp.norm, (double)dp.fac);
+                       loss_out, dp_sums, dp.norm, (double)dp.fac, lw.weight ? lw.norm : nullptr);
     LAUNCH_CHECK();
     return ST3R_OK;
 }
@@ -256,9 +263,10 @@ struct ViewBatch {
     double* dp_sums;      // [C]: sum_p w |ED - Z|
     float* v_viewmats;    // [C,4,4]
     bool exposure;        // exposures may be registered for these views (st3r_ctx_set_exposure)
+    bool weighted;        // per-pixel loss weights may be registered for these views (st3r_ctx_set_loss_weight)
     ViewBatch slice(int c0, int c1) const {
         return {v.slice(c0, c1), gt + (int64_t)c0 * v.H * v.W * 3, sums + 2 * c0, dp_sums ? dp_sums + c0 : nullptr,
-                v_viewmats ? v_viewmats + 16 * c0 : nullptr, exposure};
+                v_viewmats ? v_viewmats + 16 * c0 : nullptr, exposure, weighted};
     }
 };
 
@@ -289,9 +297,12 @@ static int step_images(st3r_ctx* ctx, const RasterOut& ro, bool with_depth, bool
 // dp.prior != NULL: the step also renders the depth map of the same lists and takes the prior's loss, which sends v_D
 // and v_alpha back.
 static int forward_and_losses(st3r_ctx* ctx, hipStream_t s, const RasterOut& ro, const ViewBatch& b, float ssim_fac,
-                              bool sums_cleared, const DepthPrior& dp, const ExposureReg& ex, const StepImages& im) {
+                              bool sums_cleared, const DepthPrior& dp, const ExposureReg& ex, const LossWeight& lw,
+                              const StepImages& im) {
     // ex.exposure != NULL: the loss compares y = E x with the ground truth (the stand-alone kernels of gs_exposure.hip, in
     // the order of the unfused chain); im.v_rgb leaves as d loss / d x, ex.v_exposure as d loss / d E of these views
+    // lw.weight != NULL: the photometric loss takes the views' per-pixel weights (on y with exposures, whose backward then
+    // sees the weighted d loss / d y)
     const bool eio = true;   // the fused path's offsets table carries the total as its last entry
     st3r_prof_begin(ctx, s, STG_BLEND_FWD);
     int rc = st3r_blend_fwd_impl(ctx, s, ro, im.rgb, im.alpha, im.last, true, eio);
@@ -302,7 +313,7 @@ static int forward_and_losses(st3r_ctx* ctx, hipStream_t s, const RasterOut& ro,
     if (ex.exposure) rc = st3r_exposure_fwd_impl(s, ro.C, ro.H, ro.W, im.rgb, ex.exposure, im.exposed);
     if (!rc)
         rc = st3r_loss_impl(ctx, s, ro.C, ro.H, ro.W, ex.exposure ? im.exposed : im.rgb, b.gt, 1.0f - ssim_fac, ssim_fac,
-                            b.sums, im.v_rgb, sums_cleared);
+                            b.sums, im.v_rgb, sums_cleared, lw);
     if (!rc && ex.exposure)
         rc = st3r_exposure_bwd_impl(ctx, s, ro.C, ro.H, ro.W, im.rgb, ex.exposure, im.v_rgb, im.v_rgb, ex.v_exposure);
     if (!rc && dp.prior)
@@ -385,6 +396,9 @@ static int train_views(st3r_ctx* ctx, hipStream_t s, const GsParams& g, const Vi
     if (rc) return rc;
     ExposureReg ex{};
     if (b.exposure) st3r_exposure_for(ctx, b.gt, v.C, v.H, v.W, &ex);
+    LossWeight lw{nullptr, nullptr, 0, 2};
+    if (b.weighted) rc = st3r_loss_weight_for(ctx, s, b.gt, v.C, v.H, v.W, &lw);
+    if (rc) return rc;
     // The one decision: with a depth prior the projection backward reads the per-pair array v_pairs (colour + depth
     // gradients, added), without one it sums the colour backward's slots itself.
     const bool need_pairs = dp.prior != nullptr;
@@ -402,7 +416,7 @@ static int train_views(st3r_ctx* ctx, hipStream_t s, const GsParams& g, const Vi
         ARENA_GET(SLOT_VSPLATS, float, ro.n_pairs * ST3R_SPLAT_STRIDE, vp);
         v_pairs = vp;
     }
-    rc = forward_and_losses(ctx, s, ro, b, f.ssim, true, dp, ex, im);
+    rc = forward_and_losses(ctx, s, ro, b, f.ssim, true, dp, ex, lw, im);
     if (rc) return rc;
     st3r_vtile_ref slots{};
     rc = blend_backward(ctx, s, ro, im, need_pairs, &slots, v_pairs);
@@ -501,6 +515,15 @@ int st3r_train_fwd_bwd_impl(st3r_ctx* ctx, hipStream_t s, const GsParams& g, con
                        "not supported in view-sharded training (clear it with st3r_ctx_set_intrinsics_grad(ctx, NULL, ...))");
         return ST3R_ERR_INVALID;
     }
+    // per-pixel loss weights registered for these views (st3r_ctx_set_loss_weight): the same rule
+    LossWeight lw;
+    rc = st3r_loss_weight_for(ctx, s, gt_images, C, v.H, v.W, &lw);
+    if (rc) return rc;
+    if (lw.weight && ctx->comm) {
+        st3r_set_error("loss weights are registered and a communicator is attached -- per-pixel loss weights are not "
+                       "supported in view-sharded training (clear them with st3r_ctx_set_loss_weight(ctx, NULL, ...))");
+        return ST3R_ERR_INVALID;
+    }
     st3r_prof_next_step(ctx);
     rc = st3r_count_settle(ctx);
     if (rc) return rc;
@@ -509,13 +532,13 @@ int st3r_train_fwd_bwd_impl(st3r_ctx* ctx, hipStream_t s, const GsParams& g, con
     if ((ctx->debug_flags & 32) && chunks < 2) chunks = 2;
     if (chunks > C) chunks = C;
     int64_t stats[3];
-    rc = train_chunks(ctx, s, g, ViewBatch{v, gt_images, sums, dp_sums, v_viewmats, ex.exposure != nullptr},
+    rc = train_chunks(ctx, s, g, ViewBatch{v, gt_images, sums, dp_sums, v_viewmats, ex.exposure != nullptr, lw.weight != nullptr},
                       LossFacs{ssim_fac, opac_fac, scale_fac},
                       reg_sums, reg_sums + 4, stats_host != nullptr, grads, &chunks, stats);
     if (rc) return rc;
     if (chunks > 1) ctx->view_chunks = chunks;
     rc = finalize_loss(s, C, v.H, v.W, sums, reg_sums, ssim_fac, (double)C, (double)opac_fac / N,
-                       (double)scale_fac / (3.0 * N), loss_out, dp_sums, dp);
+                       (double)scale_fac / (3.0 * N), loss_out, dp_sums, dp, lw);
     if (rc) return rc;
     if (stats_host) {
         stats_host[0] = stats[0]; stats_host[1] = stats[1]; stats_host[2] = st3r_ctx_arena_bytes(ctx);
@@ -546,7 +569,7 @@ ST3R_EXPORT int st3r_gs_raster_train(st3r_ctx* ctx, void* stream, int N, int C, 
     hipStream_t s = (hipStream_t)stream;
     ARENA_GET(SLOT_SMALL, double, 2 * (size_t)C + 8, sums);
     double* reg_sums = sums + 2 * C;
-    const ViewBatch b{GsViews{C, width, height}, gt_images, sums, nullptr, nullptr, false};   // (no camera is looked at)
+    const ViewBatch b{GsViews{C, width, height}, gt_images, sums, nullptr, nullptr, false, false};   // (no camera is looked at)
     HIP_TRY(hipMemsetAsync(reg_sums, 0, sizeof(double) * 4, s));  // stays zero: the regularisers belong to the owners
     st3r_prof_next_step(ctx);
     RasterOut ro;
@@ -558,13 +581,14 @@ ST3R_EXPORT int st3r_gs_raster_train(st3r_ctx* ctx, void* stream, int N, int C, 
     StepImages im;
     rc = step_images(ctx, ro, false, false, &im);
     if (rc) return rc;
-    rc = forward_and_losses(ctx, s, ro, b, ssim_fac, false, DepthPrior{}, ExposureReg{}, im);
+    const LossWeight no_weights{nullptr, nullptr, 0, 2};
+    rc = forward_and_losses(ctx, s, ro, b, ssim_fac, false, DepthPrior{}, ExposureReg{}, no_weights, im);
     if (rc) return rc;
     st3r_prof_begin(ctx, s, STG_BLEND_BWD);
     rc = st3r_blend_bwd_impl(ctx, s, ro, im.alpha, im.last, im.v_rgb, nullptr, v_records, true, nullptr);
     st3r_prof_end(ctx, s, STG_BLEND_BWD);
     if (rc) return rc;
-    rc = finalize_loss(s, C, height, width, sums, reg_sums, ssim_fac, 0.0, 0.0, 0.0, loss_out, nullptr, DepthPrior{});
+    rc = finalize_loss(s, C, height, width, sums, reg_sums, ssim_fac, 0.0, 0.0, 0.0, loss_out, nullptr, DepthPrior{}, no_weights);
     if (rc) return rc;
     if (stats_host) {
         stats_host[0] = -1; stats_host[1] = ro.n_records; stats_host[2] = st3r_ctx_arena_bytes(ctx); stats_host[3] = -1;

@@ -13,7 +13,15 @@
 //   backward: v_x = k_l1*sign(x-y) + k_ss*( G*D0 + 2x G*D1 + y G*D2 )   (G symmetric).
 // k_ssim_fwd is the forward alone (value-only calls); k_ssim_fused runs both with D kept in LDS (see there).
 // The window never touches padding for interior outputs, so reflect-padding is not needed.
-#include "stages.h"
+//
+// Per-pixel weights (WGT instantiations; st3r_loss_l1_ssim_weighted, st3r_ctx_set_loss_weight): a map w [C,H,W] >= 0
+// multiplies the L1 term of its pixel and the SSIM map AT THE WINDOW'S CENTRE -- the windows themselves stay unweighted,
+// so a pixel within 5 px (Chebyshev) of a weighted pixel still enters that pixel's window:
+//     n1 = max(sum_p w, 1)   n2 = max(sum_{p in I} w, 1)   (I: the interior)
+//     loss_c = w_l1 sum_p w sum_ch |gt - r| / (3 n1) + w_ssim sum_{p in I} w sum_ch (1 - ssim) / (3 n2)
+// The weight enters BETWEEN the two convolutions: the forward stores w D, the backward convolves that.  A pixel with
+// w == 0 contributes exact zeros (a select, not a product alone).  The unweighted instantiations are untouched by it.
+#include "per_view.h"
 
 #define LW 64                 // strip width in pixels
 #define LT (LW * 3)           // threads per workgroup: one per (column, channel)
@@ -32,6 +40,16 @@ static Win make_window() {
     return w;
 }
 
+// v under the weight w of its pixel: w v, exactly 0 where w == 0 (or is a NaN) whatever v holds.  (Only the weighted
+// instantiations call it; the unweighted ones keep their statements as they were, `if constexpr` around them: a value
+// that passes through a function is contracted into other multiply-adds than before.)
+__device__ __forceinline__ float weighted(float w, float v) { return w > 0.f ? w * v : 0.f; }
+// acc + w ssim, ssim = (n1 n2) inv, in the association the compiler gives the unweighted `acc += ssim` -- it contracts the
+// last product of ssim into the sum, fma(n1 n2, inv, acc) --, so that w == 1 gives the unweighted kernels' bits
+__device__ __forceinline__ float weighted_ssim_sum(float acc, float w, float n1n2, float inv) {
+    return w > 0.f ? __builtin_fmaf(w * n1n2, inv, acc) : acc;
+}
+
 __device__ __forceinline__ float block_sum_192(float v, float* red) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
@@ -43,9 +61,12 @@ __device__ __forceinline__ float block_sum_192(float v, float* red) {
     return t;
 }
 
+// WGT: weight [C,H,W] (see the file header); the two sums of view c go to sums[sums_stride * c + 0 / 1]
+template <bool WGT>
 __global__ __launch_bounds__(LT) void k_ssim_fwd(int LH, int H, int W, const float* __restrict__ render,
                                                  const float* __restrict__ gt, Win win,
-                                                 double* __restrict__ sums, float* __restrict__ D) {
+                                                 double* __restrict__ sums, float* __restrict__ D,
+                                                 const float* __restrict__ weight, int sums_stride) {
     __shared__ float sx[2][SEG];
     __shared__ float sy[2][SEG];
     __shared__ float red[4];
@@ -58,6 +79,8 @@ __global__ __launch_bounds__(LT) void k_ssim_fwd(int LH, int H, int W, const flo
     const float* yr = gt + (int64_t)cam * H * W * 3;
     const float c1 = 0.01f * 0.01f, c2 = 0.03f * 0.03f;
     const int nrows = min(LH, H - i0) + 2 * HALO;  // input rows i0-5 .. i0+rows+4
+    // WGT: this thread's column of the weight map (clamped, unconditional loads; what lies outside is never used)
+    const float* wcol = WGT ? weight + (int64_t)cam * H * W + min(j, W - 1) : nullptr;
 
     // Input row r (image row i0 - HALO + r) travels HBM -> registers (prefetch, issued two rows
     // ahead of its use so the load latency hides behind a whole row of arithmetic) -> LDS (commit).
@@ -117,7 +140,16 @@ __global__ __launch_bounds__(LT) void k_ssim_fwd(int LH, int H, int W, const flo
                 }
                 ring[s][0] = h0; ring[s][1] = h1; ring[s][2] = h2; ring[s][3] = h3; ring[s][4] = h4;
                 const int i = i0 - HALO + r;  // image row just staged
-                if (i >= i0 && i < i0 + LH && i < H && j < W) l1 += fabsf(py[HALO * 3] - px[HALO * 3]);
+                float wl = 1.f, wd = 1.f;     // weights of the L1 pixel (i, j) and of the output pixel (i - 5, j)
+                if (WGT) {
+                    wl = wcol[(int64_t)min(max(i, 0), H - 1) * W];
+                    wd = wcol[(int64_t)min(max(i - HALO, 0), H - 1) * W];
+                }
+                if constexpr (WGT) {
+                    if (i >= i0 && i < i0 + LH && i < H && j < W) l1 += weighted(wl, fabsf(py[HALO * 3] - px[HALO * 3]));
+                } else {
+                    if (i >= i0 && i < i0 + LH && i < H && j < W) l1 += fabsf(py[HALO * 3] - px[HALO * 3]);
+                }
                 if (r >= 2 * HALO) {
                     const int io = i0 + r - 2 * HALO;  // output row
                     float d0 = 0.f, d1 = 0.f, d2 = 0.f;
@@ -142,12 +174,14 @@ __global__ __launch_bounds__(LT) void k_ssim_fwd(int LH, int H, int W, const flo
                         const float inv1 = __builtin_amdgcn_rcpf(dd1), inv2 = __builtin_amdgcn_rcpf(dd2);
                         const float inv = inv1 * inv2;
                         const float ssim = n1 * n2 * inv;
-                        ssim_acc += ssim;
+                        if constexpr (WGT) ssim_acc = weighted_ssim_sum(ssim_acc, wd, n1 * n2, inv);
+                        else ssim_acc += ssim;
                         const float dn1 = n2 * inv, dn2 = n1 * inv;
                         const float g1 = -ssim * inv1, g2 = sxx_raw < 0.f ? 0.f : -ssim * inv2;
                         d0 = 2.f * my * (dn1 - dn2) + 2.f * mx * (g1 - g2);  // dS/dmu_x
                         d1 = g2;                                             // dS/dE[x^2]
                         d2 = 2.f * dn2;                                      // dS/dE[xy]
+                        if constexpr (WGT) { d0 = weighted(wd, d0); d1 = weighted(wd, d1); d2 = weighted(wd, d2); }
                     }
                     if (D && io < H && j < W) {
                         float* dst = D + ((((int64_t)cam * H + io) * W + j) * 3 + ch) * 3;
@@ -161,8 +195,9 @@ __global__ __launch_bounds__(LT) void k_ssim_fwd(int LH, int H, int W, const flo
     const float tl1 = block_sum_192(l1, red);
     const float tss = block_sum_192(ssim_acc, red);
     if (threadIdx.x == 0) {
-        atomicAdd(&sums[2 * cam + 0], (double)tl1);
-        atomicAdd(&sums[2 * cam + 1], (double)tss);
+        const int ss = WGT ? sums_stride : 2;
+        atomicAdd(&sums[ss * cam + 0], (double)tl1);
+        atomicAdd(&sums[ss * cam + 1], (double)tss);
     }
 }
 
@@ -291,11 +326,23 @@ __global__ __launch_bounds__(LT) void k_gt_moments(int LH, int H, int W, const f
 #ifndef SSIM_GTM_WAVES
 #define SSIM_GTM_WAVES 5
 #endif
-template <bool GTM>
-__global__ __launch_bounds__(FT2) __attribute__((amdgpu_waves_per_eu(GTM ? SSIM_GTM_WAVES : 5))) void k_ssim_fused(int LH, int H, int W, const float* __restrict__ render,
+// WGT: weight [C,H,W] (see the file header).  k_l1 and k_ss then carry w_l1 and w_ssim, and the constants of the view
+// come from its normalisers norm[norm_stride * c + 0 / 1] = sum_p w, sum_{p in I} w (k_loss_wsum; at least 1 each here):
+// k_l1_c = w_l1 / (3 n1), k_ss_c = -w_ssim / (3 n2), uniform over the workgroup.  The forward waves load w at the L1 pixel
+// and at the D pixel one iteration ahead (like the registered moments), the backward waves at their output pixel.
+#ifndef SSIM_WGT_GTM_WAVES
+#define SSIM_WGT_GTM_WAVES 5
+#endif
+#ifndef SSIM_WGT_WAVES
+#define SSIM_WGT_WAVES 4
+#endif
+template <bool GTM, bool WGT>
+__global__ __launch_bounds__(FT2) __attribute__((amdgpu_waves_per_eu(GTM ? (WGT ? SSIM_WGT_GTM_WAVES : SSIM_GTM_WAVES) : (WGT ? SSIM_WGT_WAVES : 5)))) void k_ssim_fused(int LH, int H, int W, const float* __restrict__ render,
                                                     const float* __restrict__ gt, const float2* __restrict__ gtm,
                                                     Win win_s, float k_l1, float k_ss,
-                                                    double* __restrict__ sums, float* __restrict__ v_render) {
+                                                    double* __restrict__ sums, float* __restrict__ v_render,
+                                                    const float* __restrict__ weight, const double* __restrict__ norm,
+                                                    int norm_stride, int sums_stride) {
     __shared__ float sx[2][SEG2];
     __shared__ float sy[2][SEG2];
     __shared__ float sd[2][DCOLS * 9];
@@ -359,6 +406,17 @@ __global__ __launch_bounds__(FT2) __attribute__((amdgpu_waves_per_eu(GTM ? SSIM_
         };
         float2 gq = make_float2(0.f, 0.f);
         if (GTM) gq = fetch_gtm(0);
+        // WGT: the weights of the L1 pixel (i0 + r - 10, jd) and of the D pixel (i0 + r - 15, jd) of iteration r, requested
+        // one iteration ahead with the same clamped, unconditional addressing
+        // (a scalar row pointer + one 32-bit column offset per thread, like the image rows)
+        const float* wr = WGT ? weight + (int64_t)cam * H * W : nullptr;
+        const unsigned jw = (unsigned)min(max(jd, 0), W - 1);
+        auto fetch_w = [&](int r) -> float2 {
+            const int il = min(max(i0 - HALO2 + r, 0), H - 1), idr = min(max(i0 + r - 3 * HALO, 0), H - 1);
+            return make_float2((wr + (int64_t)il * W)[jw], (wr + (int64_t)idr * W)[jw]);
+        };
+        float2 wq = make_float2(1.f, 1.f);
+        if (WGT) wq = fetch_w(0);
         fetch_row(0, qx[0], qy[0]);
         commit_from(0, qx[0], qy[0]);
 #pragma unroll
@@ -375,6 +433,8 @@ __global__ __launch_bounds__(FT2) __attribute__((amdgpu_waves_per_eu(GTM ? SSIM_
                         fetch_row(r + 1 + SSIM_PD, qx[(s + 1) % SSIM_PD], qy[(s + 1) % SSIM_PD]);
                         const float2 gcur = gq;
                         if (GTM) gq = fetch_gtm(r + 1);
+                        const float2 wcur = wq;
+                        if (WGT) wq = fetch_w(r + 1);
                         if (active) {
                             const float* px = &sx[b][col * 3 + ch];
                             const float* py = &sy[b][col * 3 + ch];
@@ -396,7 +456,11 @@ __global__ __launch_bounds__(FT2) __attribute__((amdgpu_waves_per_eu(GTM ? SSIM_
                             ring[s][0] = h0; ring[s][1] = h2; ring[s][2] = h4;
                             if (!GTM) { ring[s][NM - 2] = h1; ring[s][NM - 1] = h3; }
                             const int i = i0 - HALO2 + r;  // image row just staged
-                            if (own_col && i >= i0 && i < i0 + rows_out) l1 += fabsf(py[HALO * 3] - px[HALO * 3]);
+                            if constexpr (WGT) {
+                                if (own_col && i >= i0 && i < i0 + rows_out) l1 += weighted(wcur.x, fabsf(py[HALO * 3] - px[HALO * 3]));
+                            } else {
+                                if (own_col && i >= i0 && i < i0 + rows_out) l1 += fabsf(py[HALO * 3] - px[HALO * 3]);
+                            }
                             if (r >= 2 * HALO) {
                                 const int id = i0 + r - 3 * HALO;  // image row of the D row completed now
                                 float d0 = 0.f, d1 = 0.f, d2 = 0.f;
@@ -425,12 +489,17 @@ __global__ __launch_bounds__(FT2) __attribute__((amdgpu_waves_per_eu(GTM ? SSIM_
                                     const float inv1 = __builtin_amdgcn_rcpf(dd1), inv2 = __builtin_amdgcn_rcpf(dd2);
                                     const float inv = inv1 * inv2;
                                     const float ssim = n1 * n2 * inv;
-                                    if (own_col && id >= i0 && id < i0 + rows_out) ssim_acc += ssim;  // one strip counts it
+                                    if constexpr (WGT) {
+                                        if (own_col && id >= i0 && id < i0 + rows_out) ssim_acc = weighted_ssim_sum(ssim_acc, wcur.y, n1 * n2, inv);
+                                    } else {
+                                        if (own_col && id >= i0 && id < i0 + rows_out) ssim_acc += ssim;  // one strip counts it
+                                    }
                                     const float dn1 = n2 * inv, dn2 = n1 * inv;
                                     const float g1 = -ssim * inv1, g2 = sxx_raw < 0.f ? 0.f : -ssim * inv2;
                                     d0 = 2.f * my * (dn1 - dn2) + 2.f * mx * (g1 - g2);  // dS/dmu_x
                                     d1 = g2;                                             // dS/dE[x^2]
                                     d2 = 2.f * dn2;                                      // dS/dE[xy]
+                                    if constexpr (WGT) { d0 = weighted(wcur.y, d0); d1 = weighted(wcur.y, d1); d2 = weighted(wcur.y, d2); }
                                 }
                                 float* dst = &sd[b][col * 9 + ch * 3];
                                 dst[0] = d0; dst[1] = d1; dst[2] = d2;
@@ -451,14 +520,23 @@ __global__ __launch_bounds__(FT2) __attribute__((amdgpu_waves_per_eu(GTM ? SSIM_
         for (int s = 0; s < SSIM_U; ++s) { ring[s][0] = 0.f; ring[s][1] = 0.f; ring[s][2] = 0.f; }
         // x, y of this thread's output pixel: iteration r writes image row i0 + r - 21; requested SSIM_PD iterations ahead
         // (slot r % SSIM_PD), like the forward waves' rows
-        float bx[SSIM_PD], by[SSIM_PD];
+        float bx[SSIM_PD], by[SSIM_PD], bw[SSIM_PD];   // (bw: the weight of the same pixel, WGT only)
         const unsigned jc = (unsigned)(min(j, W - 1) * 3 + ch);   // (unconditional, clamped loads: see the forward waves)
-        auto fetch_px = [&](int r_use, float& vx, float& vy) {
+        const float* wr = WGT ? weight + (int64_t)cam * H * W : nullptr;
+        auto fetch_px = [&](int r_use, float& vx, float& vy, float& vw) {
             const int ion = min(max(i0 + r_use - 1 - 2 * HALO2, 0), H - 1);
             vx = (xr + (int64_t)ion * (W * 3))[jc]; vy = (yr + (int64_t)ion * (W * 3))[jc];
+            if (WGT) vw = (wr + (int64_t)ion * W)[(unsigned)min(j, W - 1)];
         };
 #pragma unroll
-        for (int d = 0; d < SSIM_PD; ++d) fetch_px(d, bx[d], by[d]);
+        for (int d = 0; d < SSIM_PD; ++d) { bw[d] = 1.f; fetch_px(d, bx[d], by[d], bw[d]); }
+        // the view's constants (WGT: from its normalisers, in double as the host forms the unweighted ones)
+        float kl1 = k_l1, kss = k_ss;
+        if (WGT) {
+            const double* nc = norm + (int64_t)cam * norm_stride;
+            kl1 = (float)((double)k_l1 / (3.0 * fmax(nc[0], 1.0)));
+            kss = (H > 2 * HALO && W > 2 * HALO) ? (float)(-(double)k_ss / (3.0 * fmax(nc[1], 1.0))) : 0.f;
+        }
         __syncthreads();
         for (int rb = 0; rb <= nrows; rb += SSIM_U) {
 #pragma unroll
@@ -467,8 +545,8 @@ __global__ __launch_bounds__(FT2) __attribute__((amdgpu_waves_per_eu(GTM ? SSIM_
                 if (r <= nrows) {
                     const int rp = r - 1;                 // the forward iteration whose D row is consumed now
                     const int sp = (s + SSIM_U - 1) % SSIM_U;     // its ring slot (compile time)
-                    const float x = bx[s % SSIM_PD], y = by[s % SSIM_PD];
-                    fetch_px(r + SSIM_PD, bx[s % SSIM_PD], by[s % SSIM_PD]);
+                    const float x = bx[s % SSIM_PD], y = by[s % SSIM_PD], wv = bw[s % SSIM_PD];
+                    fetch_px(r + SSIM_PD, bx[s % SSIM_PD], by[s % SSIM_PD], bw[s % SSIM_PD]);
                     if (rp >= 2 * HALO && j < W) {
                         const float* pd = &sd[rp & 1][col * 9 + ch * 3];
                         float h0 = win.w[0] * pd[0], h1 = win.w[0] * pd[1], h2 = win.w[0] * pd[2];
@@ -494,7 +572,11 @@ __global__ __launch_bounds__(FT2) __attribute__((amdgpu_waves_per_eu(GTM ? SSIM_
                                 }
                                 float* vrow = v_render + ((int64_t)cam * H + io) * (W * 3);   // (uniform row pointer)
                                 const float sgn = (x > y) ? 1.0f : ((x < y) ? -1.0f : 0.0f);
-                                vrow[(unsigned)(j * 3 + ch)] = k_l1 * sgn + k_ss * (a0 + 2.f * x * a1 + y * a2);
+                                if constexpr (WGT)
+                                    // (spelled as the compiler contracts the unweighted line below)
+                                    vrow[(unsigned)(j * 3 + ch)] = __builtin_fmaf(weighted(wv, kl1), sgn, kss * (a0 + 2.f * x * a1 + y * a2));
+                                else
+                                    vrow[(unsigned)(j * 3 + ch)] = k_l1 * sgn + k_ss * (a0 + 2.f * x * a1 + y * a2);
                             }
                         }
                     }
@@ -513,8 +595,9 @@ __global__ __launch_bounds__(FT2) __attribute__((amdgpu_waves_per_eu(GTM ? SSIM_
         float a = 0.f, b = 0.f;
 #pragma unroll
         for (int i = 0; i < FW; ++i) { a += red[i]; b += red[FW + i]; }
-        atomicAdd(&sums[2 * cam + 0], (double)a);
-        atomicAdd(&sums[2 * cam + 1], (double)b);
+        const int ss = WGT ? sums_stride : 2;
+        atomicAdd(&sums[ss * cam + 0], (double)a);
+        atomicAdd(&sums[ss * cam + 1], (double)b);
     }
 }
 
@@ -524,8 +607,77 @@ static const float2* gt_moments_for(const st3r_ctx* ctx, const float* gt, int C,
     return c0 < 0 ? nullptr : reinterpret_cast<const float2*>(ctx->gtm_mom) + c0 * H * W * 3;
 }
 
+// ---- normalisers of the per-pixel weights ----
+// part[(c, workgroup)] = (sum_p w, sum_{p in I} w) of one chunk of view c, the weights that count (w > 0) in double; a
+// streaming kernel of per_view.h.  The interior test needs the pixel's row and column: a division per access.
+template <bool VEC>
+__global__ __launch_bounds__(STREAM_T) void k_loss_wsum(int64_t HW, int64_t chunk, int H, int W,
+                                                        const float* __restrict__ weight, double* __restrict__ part) {
+    __shared__ double red[8];
+    const int c = blockIdx.y;
+    const float* w = weight + (int64_t)c * HW;
+    int64_t lo, hi;
+    stream_chunk(chunk, HW, lo, hi);
+    double acc[2] = {0.0, 0.0};
+    auto take = [&](int row, int col, float v) {
+        const double d = (double)(v > 0.f ? v : 0.f);
+        acc[0] += d;
+        if (row >= HALO && row < H - HALO && col >= HALO && col < W - HALO) acc[1] += d;
+    };
+    if (VEC) {
+        for (int64_t i = lo + 4 * (int64_t)threadIdx.x; i < hi; i += 4 * STREAM_T) {
+            const float4 v = *reinterpret_cast<const float4*>(w + i);
+            const float e[4] = {v.x, v.y, v.z, v.w};
+            int row = (int)(i / W), col = (int)(i - (int64_t)row * W);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                take(row, col, e[k]);
+                if (++col == W) { col = 0; ++row; }
+            }
+        }
+    } else {
+        for (int64_t i = lo + threadIdx.x; i < hi; i += STREAM_T) {
+            const int row = (int)(i / W);
+            take(row, (int)(i - (int64_t)row * W), w[i]);
+        }
+    }
+    const double t = block_sum_fixed(acc, red);
+    if (threadIdx.x < 2) part[((int64_t)c * gridDim.x + blockIdx.x) * 2 + threadIdx.x] = t;
+}
+
+// norm[c * stride + 0 / 1] = sum_p w, sum_{p in I} w of the views at `weight`; at_least_one: max(., 1) of each
+static int loss_weight_norms(st3r_ctx* ctx, hipStream_t s, int C, int H, int W, const float* weight, double* norm,
+                             int stride, int at_least_one) {
+    const int64_t HW = (int64_t)H * W;
+    int blocks; int64_t chunk;
+    st3r_stream_grid(C, HW, &blocks, &chunk);
+    ARENA_GET(SLOT_LWEIGHT_PART, double, (size_t)C * blocks * 2, part);
+    STREAM_LAUNCH(k_loss_wsum, HW % 4 == 0 && aligned16(weight), blocks, C, s, HW, chunk, H, W, weight, part);
+    return stream_finish<2>(s, C, blocks, part, norm, stride, at_least_one);
+}
+
+// The registered weights that belong to the C views at `gt` (fused_step.hip): out->weight = NULL if no registration
+// applies (view_reg_first).  The sums of the registration (not clamped: the finalisation needs sum_{p in I} w itself) are
+// computed by the first call that gets here, on its stream, like the depth prior's n_c.
+int st3r_loss_weight_for(st3r_ctx* ctx, hipStream_t s, const float* gt, int C, int H, int W, LossWeight* out) {
+    *out = LossWeight{nullptr, nullptr, 0, 2};
+    const int64_t c0 = view_reg_first(ctx->lw, gt, C, H, W);
+    if (c0 < 0) return ST3R_OK;
+    void* p = nullptr; int grown = 0;
+    int rc = st3r_arena_get2(ctx, SLOT_LWEIGHT_NORM, sizeof(double) * 2 * (size_t)ctx->lw.c, &p, &grown);
+    if (rc) return rc;
+    if (grown || !ctx->lw_norm_valid) {
+        rc = loss_weight_norms(ctx, s, ctx->lw.c, H, W, ctx->lw_weight, (double*)p, 2, 0);
+        if (rc) return rc;
+        ctx->lw_norm_valid = 1;
+    }
+    *out = LossWeight{ctx->lw_weight + c0 * H * W, (const double*)p + 2 * c0, 2, 2};
+    return ST3R_OK;
+}
+
+// lw.weight != NULL: the weighted loss (file header); sums then has lw.sums_stride doubles per view
 int st3r_loss_impl(st3r_ctx* ctx, hipStream_t s, int C, int H, int W, const float* render, const float* gt,
-                   float w_l1, float w_ssim, double* sums, float* v_render, bool sums_cleared) {
+                   float w_l1, float w_ssim, double* sums, float* v_render, bool sums_cleared, const LossWeight& lw) {
     static const Win win = make_window();
     if (!sums_cleared) HIP_TRY(hipMemsetAsync(sums, 0, sizeof(double) * 2 * (size_t)C, s));
     // A strip of LH output rows streams LH + 20 input rows: tall strips waste less, but the launch needs a few
@@ -543,23 +695,32 @@ int st3r_loss_impl(st3r_ctx* ctx, hipStream_t s, int C, int H, int W, const floa
     // rule above 0.453, 8 bands 0.437, 10 bands 0.416: what matters is how the workgroups fill whole rounds of the chip)
     // (the same for the kernel that convolves the ground truth itself -- 94 VGPRs, two workgroups per CU, 512 slots: 8 x 1080p
     // with 2 bands 0.436 ms, 3 bands 0.49, 4 bands 0.45, 5 bands 0.47, 6 bands 0.46)
-    if (v_render) bands = std::max(1, std::min((gtm ? 768 : 512) / std::max(per_band, 1), std::max(1, H / 64)));
+    // (the weighted instantiations -- 89 VGPRs with registered moments, 107 without -- keep two workgroups per CU: 512 slots)
+    if (v_render) bands = std::max(1, std::min((gtm && !lw.weight ? 768 : 512) / std::max(per_band, 1), std::max(1, H / 64)));
     if (const char* e = getenv("ST3R_SSIM_BANDS")) bands = std::max(1, atoi(e));   // tuning hook (tools/experiments/ssim_bands.sh)
     const int LH = ceil_div(H, bands);
     dim3 grid(ceil_div(W, strip), ceil_div(H, LH), C);
+    const float* const wgt = lw.weight;
     if (!v_render) {   // loss value only
-        hipLaunchKernelGGL(k_ssim_fwd, grid, dim3(LT), 0, s, LH, H, W, render, gt, win, sums, (float*)nullptr);
+        if (wgt)
+            hipLaunchKernelGGL(k_ssim_fwd<true>, grid, dim3(LT), 0, s, LH, H, W, render, gt, win, sums, (float*)nullptr, wgt,
+                               lw.sums_stride);
+        else
+            hipLaunchKernelGGL(k_ssim_fwd<false>, grid, dim3(LT), 0, s, LH, H, W, render, gt, win, sums, (float*)nullptr, wgt, 2);
         LAUNCH_CHECK();
         return ST3R_OK;
     }
     const int Hi = H - 2 * HALO, Wi = W - 2 * HALO;
     const double cnt = (Hi > 0 && Wi > 0) ? (double)Hi * Wi * 3 : 0.0;
-    const float k_l1 = (float)((double)w_l1 / ((double)H * W * 3));
-    const float k_ss = cnt > 0 ? (float)(-(double)w_ssim / cnt) : 0.f;
-    if (gtm)
-        hipLaunchKernelGGL(k_ssim_fused<true>, grid, dim3(FT2), 0, s, LH, H, W, render, gt, gtm, win, k_l1, k_ss, sums, v_render);
-    else
-        hipLaunchKernelGGL(k_ssim_fused<false>, grid, dim3(FT2), 0, s, LH, H, W, render, gt, gtm, win, k_l1, k_ss, sums, v_render);
+    // (weighted: the kernel forms the constants of every view from w_l1, w_ssim and the view's normalisers)
+    const float k_l1 = wgt ? w_l1 : (float)((double)w_l1 / ((double)H * W * 3));
+    const float k_ss = wgt ? w_ssim : cnt > 0 ? (float)(-(double)w_ssim / cnt) : 0.f;
+#define SSIM_FUSED_LAUNCH(GTM, WGT)                                                                                        \
+    hipLaunchKernelGGL((k_ssim_fused<GTM, WGT>), grid, dim3(FT2), 0, s, LH, H, W, render, gt, gtm, win, k_l1, k_ss, sums,   \
+                       v_render, wgt, lw.norm, lw.norm_stride, lw.sums_stride)
+    if (gtm) { if (wgt) SSIM_FUSED_LAUNCH(true, true); else SSIM_FUSED_LAUNCH(true, false); }
+    else { if (wgt) SSIM_FUSED_LAUNCH(false, true); else SSIM_FUSED_LAUNCH(false, false); }
+#undef SSIM_FUSED_LAUNCH
     LAUNCH_CHECK();
     return ST3R_OK;
 }
@@ -589,5 +750,28 @@ ST3R_EXPORT int st3r_ctx_set_gt_moments(st3r_ctx* ctx, const float* gt, const fl
 ST3R_EXPORT int st3r_loss_l1_ssim(st3r_ctx* ctx, void* stream, int C, int height, int width, const float* render,
                                   const float* gt, float w_l1, float w_ssim, double* sums, float* v_render) {
     ARG_CHECK(ctx && C > 0 && height > 0 && width > 0 && render && gt && sums);
-    return st3r_loss_impl(ctx, (hipStream_t)stream, C, height, width, render, gt, w_l1, w_ssim, sums, v_render, false);
+    return st3r_loss_impl(ctx, (hipStream_t)stream, C, height, width, render, gt, w_l1, w_ssim, sums, v_render, false,
+                          LossWeight{nullptr, nullptr, 0, 2});
+}
+
+ST3R_EXPORT int st3r_loss_l1_ssim_weighted(st3r_ctx* ctx, void* stream, int C, int height, int width, const float* render,
+                                           const float* gt, const float* weight, float w_l1, float w_ssim, double* sums,
+                                           float* v_render) {
+    ARG_CHECK(ctx && C > 0 && height > 0 && width > 0 && render && gt && weight && sums);
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(hipMemsetAsync(sums, 0, sizeof(double) * 4 * (size_t)C, s));
+    int rc = loss_weight_norms(ctx, s, C, height, width, weight, sums + 2, 4, 1);   // n1, n2 into columns 2 and 3
+    if (rc) return rc;
+    return st3r_loss_impl(ctx, s, C, height, width, render, gt, w_l1, w_ssim, sums, v_render, true,
+                          LossWeight{weight, sums + 2, 4, 4});
+}
+
+ST3R_EXPORT int st3r_ctx_set_loss_weight(st3r_ctx* ctx, const float* gt, const float* weight, int C, int height,
+                                         int width) {
+    ARG_CHECK(ctx);
+    ctx->lw_norm_valid = 0;
+    const bool on = gt && weight;
+    int rc = view_reg_set(&ctx->lw, on, gt, C, height, width);
+    if (!rc) ctx->lw_weight = on ? weight : nullptr;
+    return rc;
 }

@@ -45,6 +45,11 @@ struct DepthPrior { const float* prior; const float* weight; const double* norm;
 // the registered exposures of a set of views (gs_exposure.hip) and where their gradient goes; exposure == NULL: none applies
 struct ExposureReg { const float* exposure; float* v_exposure; };
 
+// the per-pixel loss weights of a set of views (loss.hip); weight == NULL: none apply.  weight [C,H,W]; norm: per view
+// norm_stride doubles, of which the first two are sum_p w and sum_{p in I} w (clamped to >= 1 or not: the readers clamp);
+// sums_stride: doubles per view of the loss kernel's accumulators
+struct LossWeight { const float* weight; const double* norm; int norm_stride; int sums_stride; };
+
 // ---- api.hip, fused_step.hip, comm.hip ----
 // The 16 device words next to the fused steps: [0] record count of an asynchronous step (k_adam compares it with the
 // step's capacity), [4] status word of an exchanged step (comm.hip).  Zeroed when allocated.
@@ -111,7 +116,8 @@ int st3r_add_pairs_impl(hipStream_t s, int64_t n_pairs, float* a, const float* b
 
 // ---- loss.hip, loss_depth.hip ----
 int st3r_loss_impl(st3r_ctx* ctx, hipStream_t s, int C, int H, int W, const float* render, const float* gt,
-                   float w_l1, float w_ssim, double* sums, float* v_render, bool sums_cleared);
+                   float w_l1, float w_ssim, double* sums, float* v_render, bool sums_cleared, const LossWeight& lw);
+int st3r_loss_weight_for(st3r_ctx* ctx, hipStream_t s, const float* gt, int C, int H, int W, LossWeight* out);
 // (st3r_stream_grid, which gs_exposure.hip calls too, is declared with the streaming scaffold in per_view.h)
 int st3r_depth_prior_for(st3r_ctx* ctx, hipStream_t s, const float* gt, int C, int H, int W, DepthPrior* out);
 int st3r_depth_prior_loss_impl(st3r_ctx* ctx, hipStream_t s, int C, int H, int W, const float* depth, const float* alpha,

@@ -580,6 +580,83 @@ class _Intrinsics(_PerViewOption):
         c.scene.intrinsics = _frozen_rows_kept(c.Ks, c.scene.intrinsics, self.frozen)
 
 
+def _loss_masks_key(masks, height, width):
+    """what the cached upload of scene.loss_masks is keyed by: the entries' identities and versions (a numpy map edited in
+    place is not noticed: assign a new one) and the image size"""
+    return (tuple(None if m is None else (id(m), getattr(m, "_version", None)) for m in masks), height, width)
+
+
+def _check_loss_masks(scene, masks, height, width):
+    """ValueError unless scene.loss_masks is one entry per image, each None or an [H,W] map of finite values >= 0.  The
+    values of maps that are already uploaded (same key) are not scanned again."""
+    if isinstance(masks, (np.ndarray, torch.Tensor)) or not hasattr(masks, "__len__"):
+        raise ValueError("scene.loss_masks is a list with one entry per image (None or an [H,W] map), "
+                         f"got {type(masks).__name__}")
+    if len(masks) != len(scene.imgs):
+        raise ValueError(f"scene.loss_masks holds {len(masks)} entries for {len(scene.imgs)} images")
+    for i, m in enumerate(masks):
+        if m is not None and tuple(getattr(m, "shape", ())) != (height, width):
+            raise ValueError(f"scene.loss_masks[{i}] has shape {tuple(getattr(m, 'shape', ()))}, its image "
+                             f"({height}, {width})")
+    cached = getattr(scene, "_loss_mask_dev", None)
+    if cached is not None and cached[0] == _loss_masks_key(masks, height, width):
+        return
+    for i, m in enumerate(masks):
+        if m is None:
+            continue
+        t = m if isinstance(m, torch.Tensor) else torch.as_tensor(np.asarray(m))
+        if t.dtype == torch.bool:
+            continue
+        if t.is_complex() or not bool(torch.isfinite(t).all()) or bool((t < 0).any()):
+            raise ValueError(f"scene.loss_masks[{i}] holds negative or non-finite entries: weights are finite and >= 0")
+
+
+def _loss_masks_on_device(scene, masks, views, height, width):
+    """the weight maps of `views` ([views,H,W] float32, contiguous; None entries are all ones), uploaded once and cached
+    like the depth prior's maps"""
+    key = _loss_masks_key(masks, height, width)
+    cached = getattr(scene, "_loss_mask_dev", None)
+    if cached is None or cached[0] != key or cached[1] != tuple(views):
+        def on_device(m):
+            if m is None:
+                return torch.ones((height, width), dtype=torch.float32, device=scene.device)
+            m = m if isinstance(m, torch.Tensor) else torch.as_tensor(np.asarray(m))
+            return m.detach().to(scene.device, torch.float32)
+        w = torch.stack([on_device(masks[i]) for i in views]).contiguous()
+        scene._loss_mask_dev = (key, tuple(views), w, list(masks))   # (the entries are kept: their ids stay theirs)
+    return scene._loss_mask_dev[2]
+
+
+class _LossMasks(_PerViewOption):
+    """scene.loss_masks: per-pixel weights of the photometric loss, registered with the ctx for the fused step's weighted
+    L1 + SSIM"""
+    spelled, schedule = "scene.loss_masks", False
+
+    @classmethod
+    def when_on(cls, scene, enable_pruning, masks):
+        """switched on by a list, not by a rate: off when absent, None, or every entry None"""
+        if masks is None:
+            return None
+        height, width = scene.imgs[0].shape[:2]
+        _check_loss_masks(scene, masks, height, width)
+        if all(m is None for m in masks):
+            return None
+        _single_replica_only(cls.spelled, scene, enable_pruning)
+        return cls(scene, masks)
+
+    def __init__(self, scene, masks):
+        self.masks = masks
+
+    def set_up(self, c):
+        self.weights = _loss_masks_on_device(c.scene, self.masks, c.views, c.height, c.width)
+
+    def register(self, c):
+        ops.set_loss_weight(c.ctx, c.gt, self.weights)
+
+    def clear(self, c):
+        ops.set_loss_weight(c.ctx, None, None)
+
+
 def _iterations(iters, verbose):
     """range(iters), with a progress bar when verbose"""
     if verbose:
@@ -669,13 +746,28 @@ def run_3dgs_optim(
     with pose_lr and with at least one frozen view, so that the other views' geometry decides between the two.  Works
     together with pose_lr, depth_fac, exposure_lr and enable_pruning; single process, Gaussians replicated only.  With
     intrinsics_lr == 0 nothing about the call changes and scene.intrinsics is not touched.
+
+    scene.loss_masks (not in the reference; a setting of the scene like intrinsics_lr, default absent or None): a list with
+    one entry per image, each None (all ones) or an [H,W] array or tensor, bool or numeric, finite and >= 0 -- the weight of
+    every pixel in the photometric loss of its view: 0 drops the pixel (a passer-by, the sky, a watermark), 1 is the plain
+    loss, anything else is allowed, so a confidence can be used directly.  Per view, with I the SSIM interior,
+    loss = (1 - ssim_fac) sum_p w |gt - r| / (3 max(sum_p w, 1)) + ssim_fac sum_{p in I} w (1 - ssim) / (3 max(sum_I w, 1)).
+    The weight multiplies the SSIM map at the centre of the 11 x 11 window; the windows themselves stay unweighted, so a
+    pixel within 5 px (Chebyshev distance) of a weighted pixel still enters that pixel's window: grow a mask by 5 px to keep
+    something out entirely.  A view whose weights are all zero contributes nothing.  The regularisers and the depth term
+    (which keeps its own weights) are unchanged; the returned losses are the weighted ones.  Wrong count, wrong shape,
+    negative or non-finite entries raise ValueError before anything runs.  The maps are uploaded once and cached (keyed by
+    the entries' identities and versions: assign a new array instead of editing one in place).  Works together with
+    pose_lr, depth_fac, exposure_lr, scene.intrinsics_lr and enable_pruning; single process, Gaussians replicated only.
+    With loss_masks absent, None, or every entry None nothing about the call changes and nothing is registered.
     """
+    masks = _LossMasks.when_on(scene, enable_pruning, getattr(scene, "loss_masks", None))   # (its checks come first)
     depth = _DepthPrior.when_on(scene, enable_pruning, depth_fac, depth_conf_thres)
     poses = _Poses.when_on(scene, enable_pruning, pose_lr, pose_freeze)
     exposures = _Exposures.when_on(scene, enable_pruning, exposure_lr, exposure_freeze)
     intrinsics = _Intrinsics.when_on(scene, enable_pruning, getattr(scene, "intrinsics_lr", 0.0))
     # in this order at every hook: checks (above), set-up, registration, clearing, behind the step, finish
-    options = [o for o in (depth, poses, exposures, intrinsics) if o is not None]
+    options = [o for o in (depth, poses, exposures, intrinsics, masks) if o is not None]
     counters = [o.counter for o in options if o.counter]
     height, width = scene.imgs[0].shape[:2]
     ctx = ops.get_context(scene.device)

@@ -315,6 +315,31 @@ def set_gt_moments(ctx, gt, moments):
                       lambda: moments.is_contiguous() and moments.shape == (*gt.shape, 2))
 
 
+def loss_l1_ssim_weighted(ctx, render, gt, weight, w_l1, w_ssim, want_grad=True):
+    """L1 + SSIM of render against gt [C,H,W,3] under per-pixel weights [C,H,W] float32 >= 0
+    (st3r_loss_l1_ssim_weighted): the weight multiplies the L1 term of its pixel and the SSIM map at the window's centre.
+    Returns (sums [C,4] float64: sum_p w |gt - r|, sum_I w ssim, n1 = max(sum_p w, 1), n2 = max(sum_I w, 1) per view,
+    v_render or None)."""
+    Cn, H, W = render.shape[0], render.shape[1], render.shape[2]
+    if tuple(weight.shape) != (Cn, H, W) or weight.dtype != torch.float32 or not weight.is_contiguous():
+        raise ValueError(f"expected contiguous float32 weights {(Cn, H, W)}, got {weight.dtype} {tuple(weight.shape)}")
+    sums = torch.empty((Cn, 4), dtype=torch.float64, device=render.device)
+    v = torch.empty_like(render) if want_grad else None
+    _lib.check(_lib.lib().st3r_loss_l1_ssim_weighted(ctx.handle, _stream(), Cn, H, W, _p(render), _p(gt), _p(weight), w_l1,
+                                                     w_ssim, _p(sums, torch.float64), _p(v)))
+    return sums, v
+
+
+def set_loss_weight(ctx, gt, weight):
+    """Register the per-pixel loss weights [C,H,W] (float32, >= 0) of the images gt [C,H,W,3] with the ctx -- train_fwd_bwd,
+    train_step and train_step_poses on `gt` (or whole views of it) then take the weighted loss of loss_l1_ssim_weighted
+    (st3r_ctx_set_loss_weight) -- or clear the registration (gt = None).  The caller's tensors are kept alive here and must
+    stay unchanged while registered."""
+    _set_registration(ctx, "loss_weight", "_lw_keep", gt, (weight,),
+                      lambda: weight.is_contiguous() and weight.dtype == torch.float32 and
+                      weight.shape == tuple(gt.shape[:3]))
+
+
 def loss_depth_prior(ctx, depth, alpha, prior, weight, depth_fac):
     """Weighted L1 between the expected depth ED = depth / max(alpha, 1e-10) of a render (depth, alpha [C,H,W,1]) and a
     prior [C,H,W] under weights [C,H,W] >= 0 (st3r_loss_depth_prior).  Returns (sums [C,2] float64: sum_p w |ED - Z| and
