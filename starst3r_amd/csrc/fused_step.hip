@@ -396,7 +396,7 @@ static int train_views(st3r_ctx* ctx, hipStream_t s, const GsParams& g, const Vi
     if (rc) return rc;
     ExposureReg ex{};
     if (b.exposure) st3r_exposure_for(ctx, b.gt, v.C, v.H, v.W, &ex);
-    LossWeight lw{nullptr, nullptr, 0, 2};
+    LossWeight lw{};
     if (b.weighted) rc = st3r_loss_weight_for(ctx, s, b.gt, v.C, v.H, v.W, &lw);
     if (rc) return rc;
     // The one decision: with a depth prior the projection backward reads the per-pair array v_pairs (colour + depth
@@ -581,14 +581,14 @@ ST3R_EXPORT int st3r_gs_raster_train(st3r_ctx* ctx, void* stream, int N, int C, 
     StepImages im;
     rc = step_images(ctx, ro, false, false, &im);
     if (rc) return rc;
-    const LossWeight no_weights{nullptr, nullptr, 0, 2};
-    rc = forward_and_losses(ctx, s, ro, b, ssim_fac, false, DepthPrior{}, ExposureReg{}, no_weights, im);
+    rc = forward_and_losses(ctx, s, ro, b, ssim_fac, false, DepthPrior{}, ExposureReg{}, LossWeight{}, im);
     if (rc) return rc;
     st3r_prof_begin(ctx, s, STG_BLEND_BWD);
     rc = st3r_blend_bwd_impl(ctx, s, ro, im.alpha, im.last, im.v_rgb, nullptr, v_records, true, nullptr);
     st3r_prof_end(ctx, s, STG_BLEND_BWD);
     if (rc) return rc;
-    rc = finalize_loss(s, C, height, width, sums, reg_sums, ssim_fac, 0.0, 0.0, 0.0, loss_out, nullptr, DepthPrior{}, no_weights);
+    rc = finalize_loss(s, C, height, width, sums, reg_sums, ssim_fac, 0.0, 0.0, 0.0, loss_out, nullptr, DepthPrior{},
+                       LossWeight{});
     if (rc) return rc;
     if (stats_host) {
         stats_host[0] = -1; stats_host[1] = ro.n_records; stats_host[2] = st3r_ctx_arena_bytes(ctx); stats_host[3] = -1;

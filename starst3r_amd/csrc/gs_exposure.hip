@@ -117,7 +117,7 @@ __global__ __launch_bounds__(STREAM_T) void k_exposure_bwd(int64_t HW, int64_t c
 int st3r_exposure_fwd_impl(hipStream_t s, int C, int H, int W, const float* rgb, const float* exposure, float* out) {
     const int64_t HW = (int64_t)H * W;
     int blocks; int64_t chunk;
-    st3r_stream_grid(C, HW, &blocks, &chunk);
+    stream_grid(C, HW, &blocks, &chunk);
     STREAM_LAUNCH(k_exposure_fwd, HW % 4 == 0 && aligned16(rgb, out), blocks, C, s, HW, chunk, rgb, exposure, out);
     return ST3R_OK;
 }
@@ -126,7 +126,7 @@ int st3r_exposure_bwd_impl(st3r_ctx* ctx, hipStream_t s, int C, int H, int W, co
                            const float* v_out, float* v_rgb, float* v_exposure) {
     const int64_t HW = (int64_t)H * W;
     int blocks; int64_t chunk;
-    st3r_stream_grid(C, HW, &blocks, &chunk);
+    stream_grid(C, HW, &blocks, &chunk);
     ARENA_GET(SLOT_EXPOSURE_PART, double, (size_t)C * blocks * 12, part);
     STREAM_LAUNCH(k_exposure_bwd, HW % 4 == 0 && aligned16(rgb, v_out, v_rgb), blocks, C, s, HW, chunk, rgb, exposure,
                   v_out, v_rgb, part);

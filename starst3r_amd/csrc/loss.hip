@@ -30,6 +30,8 @@
 #define SEG ((LW + 2 * HALO) * 3)   // floats per staged row segment of an image (222)
 #define SEGD ((LW + 2 * HALO) * 9)  // floats per staged row segment of D (666)
 
+static_assert(HALO == WEIGHT_SUM_BORDER, "k_weight_sums sums the weights over the interior of these kernels");
+
 struct Win { float w[KS]; };
 
 static Win make_window() {
@@ -39,16 +41,54 @@ static Win make_window() {
     for (int i = 0; i < KS; ++i) w.w[i] = (float)(g[i] / s);
     return w;
 }
+static const Win& loss_window() {
+    static const Win win = make_window();
+    return win;
+}
 
-// v under the weight w of its pixel: w v, exactly 0 where w == 0 (or is a NaN) whatever v holds.  (Only the weighted
-// instantiations call it; the unweighted ones keep their statements as they were, `if constexpr` around them: a value
-// that passes through a function is contracted into other multiply-adds than before.)
-__device__ __forceinline__ float weighted(float w, float v) { return w > 0.f ? w * v : 0.f; }
+// v under the weight w of its pixel: w v, exactly 0 where w == 0 (or is a NaN) whatever v holds; the unweighted
+// instantiations get v itself.  Every v that goes through here is a finished value (a difference, a derivative out of
+// SSIM_POINT, a constant): no product of its own is left for the compiler to contract into the caller's sums, and the
+// unweighted kernels keep the instructions they had with the statements written out (compared on the gfx950 assembly).
+template <bool WGT>
+__device__ __forceinline__ float weighted(float w, float v) { return WGT ? (w > 0.f ? w * v : 0.f) : v; }
 // acc + w ssim, ssim = (n1 n2) inv, in the association the compiler gives the unweighted `acc += ssim` -- it contracts the
-// last product of ssim into the sum, fma(n1 n2, inv, acc) --, so that w == 1 gives the unweighted kernels' bits
+// last product of ssim into the sum, fma(n1 n2, inv, acc) --, so that w == 1 gives the unweighted kernels' bits.
+// The unweighted sum stays `acc += ssim` beside the call (profiles/loss_refactor.md): `acc + ssim` in a function makes its
+// 12 v_fma_f32 v_add_f32, a spelled-out fma under the condition costs k_ssim_fused<*, false> 12 s_and_saveexec_b64
+// regions, and the fma taken before the condition takes the `w > 0` branches out of k_ssim_fused<*, true>.
 __device__ __forceinline__ float weighted_ssim_sum(float acc, float w, float n1n2, float inv) {
     return w > 0.f ? __builtin_fmaf(w * n1n2, inv, acc) : acc;
 }
+
+// The SSIM of one (pixel, channel) from its five windowed moments: the derivatives dS/dmu_x, dS/dE[x^2], dS/dE[xy] go to
+// d0, d1, d2, and between the value and the derivatives runs SUM, the caller's statement that adds the value to its sum;
+// it sees ssim = n1n2 * inv and the two factors, for the sum that takes the product apart (weighted_ssim_sum).
+// A macro like the taps below, not a function, because where the sum stands decides what the compiler makes of the
+// unweighted kernels (profiles/loss_refactor.md): a function returning {n1n2, inv, ssim, d0, d1, d2} with the sum after it
+// reorders k_ssim_fused<*, false> -- <false, false> then measured 0.437 ms against 0.433 at 8 x 1080p --, one function for
+// the value and one for the derivatives adds 12 s_nop to <true, false>, the sum as a lambda changes the opcodes of all four.
+#define SSIM_POINT(mx, my, exx, eyy, exy, d0, d1, d2, SUM)                                                               \
+    {                                                                                                                    \
+        const float c1 = 0.01f * 0.01f, c2 = 0.03f * 0.03f;                                                              \
+        /* variances clamped at 0 like torchmetrics (torch.clamp(E[x^2] - mu^2, min=0)): float cancellation on flat */   \
+        /* regions would otherwise leave them slightly negative; a clamped sigma_x^2 passes no gradient */               \
+        const float sxx_raw = (exx) - (mx) * (mx);                                                                       \
+        const float sxx = fmaxf(sxx_raw, 0.f), syy = fmaxf((eyy) - (my) * (my), 0.f), sxy = (exy) - (mx) * (my);         \
+        const float n1 = 2.f * (mx) * (my) + c1, n2 = 2.f * sxy + c2;                                                    \
+        const float dd1 = (mx) * (mx) + (my) * (my) + c1, dd2 = sxx + syy + c2;                                          \
+        /* v_rcp_f32 (1 ulp) instead of three IEEE divisions (~10 instructions each): the kernels are VALU bound and */  \
+        /* the parity bar on SSIM is 1e-5 */                                                                             \
+        const float inv1 = __builtin_amdgcn_rcpf(dd1), inv2 = __builtin_amdgcn_rcpf(dd2);                                \
+        const float inv = inv1 * inv2, n1n2 = n1 * n2;                                                                   \
+        const float ssim = n1 * n2 * inv;                                                                                \
+        SUM                                                                                                              \
+        const float dn1 = n2 * inv, dn2 = n1 * inv;                                                                      \
+        const float g1 = -ssim * inv1, g2 = sxx_raw < 0.f ? 0.f : -ssim * inv2;                                          \
+        d0 = 2.f * (my) * (dn1 - dn2) + 2.f * (mx) * (g1 - g2);                                                          \
+        d1 = g2;                                                                                                         \
+        d2 = 2.f * dn2;                                                                                                  \
+    }
 
 __device__ __forceinline__ float block_sum_192(float v, float* red) {
 #pragma unroll
@@ -77,7 +117,6 @@ __global__ __launch_bounds__(LT) void k_ssim_fwd(int LH, int H, int W, const flo
     const int j = j0 + col;
     const float* xr = render + (int64_t)cam * H * W * 3;
     const float* yr = gt + (int64_t)cam * H * W * 3;
-    const float c1 = 0.01f * 0.01f, c2 = 0.03f * 0.03f;
     const int nrows = min(LH, H - i0) + 2 * HALO;  // input rows i0-5 .. i0+rows+4
     // WGT: this thread's column of the weight map (clamped, unconditional loads; what lies outside is never used)
     const float* wcol = WGT ? weight + (int64_t)cam * H * W + min(j, W - 1) : nullptr;
@@ -145,11 +184,7 @@ __global__ __launch_bounds__(LT) void k_ssim_fwd(int LH, int H, int W, const flo
                     wl = wcol[(int64_t)min(max(i, 0), H - 1) * W];
                     wd = wcol[(int64_t)min(max(i - HALO, 0), H - 1) * W];
                 }
-                if constexpr (WGT) {
-                    if (i >= i0 && i < i0 + LH && i < H && j < W) l1 += weighted(wl, fabsf(py[HALO * 3] - px[HALO * 3]));
-                } else {
-                    if (i >= i0 && i < i0 + LH && i < H && j < W) l1 += fabsf(py[HALO * 3] - px[HALO * 3]);
-                }
+                if (i >= i0 && i < i0 + LH && i < H && j < W) l1 += weighted<WGT>(wl, fabsf(py[HALO * 3] - px[HALO * 3]));
                 if (r >= 2 * HALO) {
                     const int io = i0 + r - 2 * HALO;  // output row
                     float d0 = 0.f, d1 = 0.f, d2 = 0.f;
@@ -163,25 +198,11 @@ __global__ __launch_bounds__(LT) void k_ssim_fwd(int LH, int H, int W, const flo
                             mx += w * ring[slot][0]; my += w * ring[slot][1]; exx += w * ring[slot][2];
                             eyy += w * ring[slot][3]; exy += w * ring[slot][4];
                         }
-                        // variances clamped at 0 like torchmetrics (torch.clamp(E[x^2] - mu^2, min=0)): float cancellation on flat
-                        // regions would otherwise leave them slightly negative; a clamped sigma_x^2 passes no gradient
-                        const float sxx_raw = exx - mx * mx;
-                        const float sxx = fmaxf(sxx_raw, 0.f), syy = fmaxf(eyy - my * my, 0.f), sxy = exy - mx * my;
-                        const float n1 = 2.f * mx * my + c1, n2 = 2.f * sxy + c2;
-                        const float dd1 = mx * mx + my * my + c1, dd2 = sxx + syy + c2;
-                        // v_rcp_f32 (1 ulp) instead of three IEEE divisions (~10 instructions each): the kernel is
-                        // VALU bound and the parity bar on SSIM is 1e-5
-                        const float inv1 = __builtin_amdgcn_rcpf(dd1), inv2 = __builtin_amdgcn_rcpf(dd2);
-                        const float inv = inv1 * inv2;
-                        const float ssim = n1 * n2 * inv;
-                        if constexpr (WGT) ssim_acc = weighted_ssim_sum(ssim_acc, wd, n1 * n2, inv);
-                        else ssim_acc += ssim;
-                        const float dn1 = n2 * inv, dn2 = n1 * inv;
-                        const float g1 = -ssim * inv1, g2 = sxx_raw < 0.f ? 0.f : -ssim * inv2;
-                        d0 = 2.f * my * (dn1 - dn2) + 2.f * mx * (g1 - g2);  // dS/dmu_x
-                        d1 = g2;                                             // dS/dE[x^2]
-                        d2 = 2.f * dn2;                                      // dS/dE[xy]
-                        if constexpr (WGT) { d0 = weighted(wd, d0); d1 = weighted(wd, d1); d2 = weighted(wd, d2); }
+                        SSIM_POINT(mx, my, exx, eyy, exy, d0, d1, d2, {
+                            if constexpr (WGT) ssim_acc = weighted_ssim_sum(ssim_acc, wd, n1n2, inv);
+                            else ssim_acc += ssim;
+                        })
+                        d0 = weighted<WGT>(wd, d0); d1 = weighted<WGT>(wd, d1); d2 = weighted<WGT>(wd, d2);
                     }
                     if (D && io < H && j < W) {
                         float* dst = D + ((((int64_t)cam * H + io) * W + j) * 3 + ch) * 3;
@@ -327,7 +348,7 @@ __global__ __launch_bounds__(LT) void k_gt_moments(int LH, int H, int W, const f
 #define SSIM_GTM_WAVES 5
 #endif
 // WGT: weight [C,H,W] (see the file header).  k_l1 and k_ss then carry w_l1 and w_ssim, and the constants of the view
-// come from its normalisers norm[norm_stride * c + 0 / 1] = sum_p w, sum_{p in I} w (k_loss_wsum; at least 1 each here):
+// come from its normalisers norm[norm_stride * c + 0 / 1] = sum_p w, sum_{p in I} w (k_weight_sums; at least 1 each here):
 // k_l1_c = w_l1 / (3 n1), k_ss_c = -w_ssim / (3 n2), uniform over the workgroup.  The forward waves load w at the L1 pixel
 // and at the D pixel one iteration ahead (like the registered moments), the backward waves at their output pixel.
 #ifndef SSIM_WGT_GTM_WAVES
@@ -362,7 +383,6 @@ __global__ __launch_bounds__(FT2) __attribute__((amdgpu_waves_per_eu(GTM ? (WGT 
         const int col = t / 3, ch = t - col * 3;
         const bool active = t < DCOLS * 3;
         const int jd = j0 - HALO + col;
-        const float c1 = 0.01f * 0.01f, c2 = 0.03f * 0.03f;
         float qx[SSIM_PD][NPF2], qy[SSIM_PD][NPF2];   // rows r+1 .. r+SSIM_PD at the top of iteration r; row q in slot q % SSIM_PD
         // The loads are UNCONDITIONAL (row and column clamped into the image): a load behind a branch makes the compiler
         // wait for every load in flight at the next join, which undoes the queue.  What a clamped address delivers outside
@@ -456,11 +476,7 @@ __global__ __launch_bounds__(FT2) __attribute__((amdgpu_waves_per_eu(GTM ? (WGT 
                             ring[s][0] = h0; ring[s][1] = h2; ring[s][2] = h4;
                             if (!GTM) { ring[s][NM - 2] = h1; ring[s][NM - 1] = h3; }
                             const int i = i0 - HALO2 + r;  // image row just staged
-                            if constexpr (WGT) {
-                                if (own_col && i >= i0 && i < i0 + rows_out) l1 += weighted(wcur.x, fabsf(py[HALO * 3] - px[HALO * 3]));
-                            } else {
-                                if (own_col && i >= i0 && i < i0 + rows_out) l1 += fabsf(py[HALO * 3] - px[HALO * 3]);
-                            }
+                            if (own_col && i >= i0 && i < i0 + rows_out) l1 += weighted<WGT>(wcur.x, fabsf(py[HALO * 3] - px[HALO * 3]));
                             if (r >= 2 * HALO) {
                                 const int id = i0 + r - 3 * HALO;  // image row of the D row completed now
                                 float d0 = 0.f, d1 = 0.f, d2 = 0.f;
@@ -480,26 +496,13 @@ __global__ __launch_bounds__(FT2) __attribute__((amdgpu_waves_per_eu(GTM ? (WGT 
                                         mx += w * ring[slot][0]; exx += w * ring[slot][1]; exy += w * ring[slot][2];
                                         if (!GTM) { VMOM_TAP(my, w, ring[slot][NM - 2]) VMOM_TAP(eyy, w, ring[slot][NM - 1]) }
                                     }
-                                    // variances clamped at 0 like torchmetrics (torch.clamp(E[x^2] - mu^2, min=0)): float cancellation on flat
-                        // regions would otherwise leave them slightly negative; a clamped sigma_x^2 passes no gradient
-                        const float sxx_raw = exx - mx * mx;
-                        const float sxx = fmaxf(sxx_raw, 0.f), syy = fmaxf(eyy - my * my, 0.f), sxy = exy - mx * my;
-                                    const float n1 = 2.f * mx * my + c1, n2 = 2.f * sxy + c2;
-                                    const float dd1 = mx * mx + my * my + c1, dd2 = sxx + syy + c2;
-                                    const float inv1 = __builtin_amdgcn_rcpf(dd1), inv2 = __builtin_amdgcn_rcpf(dd2);
-                                    const float inv = inv1 * inv2;
-                                    const float ssim = n1 * n2 * inv;
-                                    if constexpr (WGT) {
-                                        if (own_col && id >= i0 && id < i0 + rows_out) ssim_acc = weighted_ssim_sum(ssim_acc, wcur.y, n1 * n2, inv);
-                                    } else {
-                                        if (own_col && id >= i0 && id < i0 + rows_out) ssim_acc += ssim;  // one strip counts it
-                                    }
-                                    const float dn1 = n2 * inv, dn2 = n1 * inv;
-                                    const float g1 = -ssim * inv1, g2 = sxx_raw < 0.f ? 0.f : -ssim * inv2;
-                                    d0 = 2.f * my * (dn1 - dn2) + 2.f * mx * (g1 - g2);  // dS/dmu_x
-                                    d1 = g2;                                             // dS/dE[x^2]
-                                    d2 = 2.f * dn2;                                      // dS/dE[xy]
-                                    if constexpr (WGT) { d0 = weighted(wcur.y, d0); d1 = weighted(wcur.y, d1); d2 = weighted(wcur.y, d2); }
+                                    SSIM_POINT(mx, my, exx, eyy, exy, d0, d1, d2, {
+                                        if (own_col && id >= i0 && id < i0 + rows_out) {   // one strip counts it
+                                            if constexpr (WGT) ssim_acc = weighted_ssim_sum(ssim_acc, wcur.y, n1n2, inv);
+                                            else ssim_acc += ssim;
+                                        }
+                                    })
+                                    d0 = weighted<WGT>(wcur.y, d0); d1 = weighted<WGT>(wcur.y, d1); d2 = weighted<WGT>(wcur.y, d2);
                                 }
                                 float* dst = &sd[b][col * 9 + ch * 3];
                                 dst[0] = d0; dst[1] = d1; dst[2] = d2;
@@ -572,11 +575,9 @@ __global__ __launch_bounds__(FT2) __attribute__((amdgpu_waves_per_eu(GTM ? (WGT 
                                 }
                                 float* vrow = v_render + ((int64_t)cam * H + io) * (W * 3);   // (uniform row pointer)
                                 const float sgn = (x > y) ? 1.0f : ((x < y) ? -1.0f : 0.0f);
-                                if constexpr (WGT)
-                                    // (spelled as the compiler contracts the unweighted line below)
-                                    vrow[(unsigned)(j * 3 + ch)] = __builtin_fmaf(weighted(wv, kl1), sgn, kss * (a0 + 2.f * x * a1 + y * a2));
-                                else
-                                    vrow[(unsigned)(j * 3 + ch)] = k_l1 * sgn + k_ss * (a0 + 2.f * x * a1 + y * a2);
+                                // (the fma is spelled out: both forms round k_ss (...) and fuse k_l1 sgn, which is what the
+                                // compiler made of `k_l1 * sgn + k_ss * (...)` -- the same instructions for both as before)
+                                vrow[(unsigned)(j * 3 + ch)] = __builtin_fmaf(weighted<WGT>(wv, kl1), sgn, kss * (a0 + 2.f * x * a1 + y * a2));
                             }
                         }
                     }
@@ -607,100 +608,52 @@ static const float2* gt_moments_for(const st3r_ctx* ctx, const float* gt, int C,
     return c0 < 0 ? nullptr : reinterpret_cast<const float2*>(ctx->gtm_mom) + c0 * H * W * 3;
 }
 
-// ---- normalisers of the per-pixel weights ----
-// part[(c, workgroup)] = (sum_p w, sum_{p in I} w) of one chunk of view c, the weights that count (w > 0) in double; a
-// streaming kernel of per_view.h.  The interior test needs the pixel's row and column: a division per access.
-template <bool VEC>
-__global__ __launch_bounds__(STREAM_T) void k_loss_wsum(int64_t HW, int64_t chunk, int H, int W,
-                                                        const float* __restrict__ weight, double* __restrict__ part) {
-    __shared__ double red[8];
-    const int c = blockIdx.y;
-    const float* w = weight + (int64_t)c * HW;
-    int64_t lo, hi;
-    stream_chunk(chunk, HW, lo, hi);
-    double acc[2] = {0.0, 0.0};
-    auto take = [&](int row, int col, float v) {
-        const double d = (double)(v > 0.f ? v : 0.f);
-        acc[0] += d;
-        if (row >= HALO && row < H - HALO && col >= HALO && col < W - HALO) acc[1] += d;
-    };
-    if (VEC) {
-        for (int64_t i = lo + 4 * (int64_t)threadIdx.x; i < hi; i += 4 * STREAM_T) {
-            const float4 v = *reinterpret_cast<const float4*>(w + i);
-            const float e[4] = {v.x, v.y, v.z, v.w};
-            int row = (int)(i / W), col = (int)(i - (int64_t)row * W);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                take(row, col, e[k]);
-                if (++col == W) { col = 0; ++row; }
-            }
-        }
-    } else {
-        for (int64_t i = lo + threadIdx.x; i < hi; i += STREAM_T) {
-            const int row = (int)(i / W);
-            take(row, (int)(i - (int64_t)row * W), w[i]);
-        }
-    }
-    const double t = block_sum_fixed(acc, red);
-    if (threadIdx.x < 2) part[((int64_t)c * gridDim.x + blockIdx.x) * 2 + threadIdx.x] = t;
-}
-
-// norm[c * stride + 0 / 1] = sum_p w, sum_{p in I} w of the views at `weight`; at_least_one: max(., 1) of each
-static int loss_weight_norms(st3r_ctx* ctx, hipStream_t s, int C, int H, int W, const float* weight, double* norm,
-                             int stride, int at_least_one) {
-    const int64_t HW = (int64_t)H * W;
-    int blocks; int64_t chunk;
-    st3r_stream_grid(C, HW, &blocks, &chunk);
-    ARENA_GET(SLOT_LWEIGHT_PART, double, (size_t)C * blocks * 2, part);
-    STREAM_LAUNCH(k_loss_wsum, HW % 4 == 0 && aligned16(weight), blocks, C, s, HW, chunk, H, W, weight, part);
-    return stream_finish<2>(s, C, blocks, part, norm, stride, at_least_one);
-}
-
 // The registered weights that belong to the C views at `gt` (fused_step.hip): out->weight = NULL if no registration
-// applies (view_reg_first).  The sums of the registration (not clamped: the finalisation needs sum_{p in I} w itself) are
-// computed by the first call that gets here, on its stream, like the depth prior's n_c.
+// applies (view_reg_first).  The sums of the registration are not clamped: the finalisation needs sum_{p in I} w itself.
 int st3r_loss_weight_for(st3r_ctx* ctx, hipStream_t s, const float* gt, int C, int H, int W, LossWeight* out) {
-    *out = LossWeight{nullptr, nullptr, 0, 2};
+    *out = LossWeight{};
     const int64_t c0 = view_reg_first(ctx->lw, gt, C, H, W);
     if (c0 < 0) return ST3R_OK;
-    void* p = nullptr; int grown = 0;
-    int rc = st3r_arena_get2(ctx, SLOT_LWEIGHT_NORM, sizeof(double) * 2 * (size_t)ctx->lw.c, &p, &grown);
+    const double* norms;
+    int rc = st3r_registered_weight_norms(ctx, s, ctx->lw, ctx->lw_weight, 0, true, SLOT_LWEIGHT_PART, SLOT_LWEIGHT_NORM,
+                                          &ctx->lw_norm_valid, &norms);
     if (rc) return rc;
-    if (grown || !ctx->lw_norm_valid) {
-        rc = loss_weight_norms(ctx, s, ctx->lw.c, H, W, ctx->lw_weight, (double*)p, 2, 0);
-        if (rc) return rc;
-        ctx->lw_norm_valid = 1;
-    }
-    *out = LossWeight{ctx->lw_weight + c0 * H * W, (const double*)p + 2 * c0, 2, 2};
+    *out = LossWeight{ctx->lw_weight + c0 * H * W, norms + 2 * c0, 2, 2};
     return ST3R_OK;
 }
 
-// lw.weight != NULL: the weighted loss (file header); sums then has lw.sums_stride doubles per view
-int st3r_loss_impl(st3r_ctx* ctx, hipStream_t s, int C, int H, int W, const float* render, const float* gt,
-                   float w_l1, float w_ssim, double* sums, float* v_render, bool sums_cleared, const LossWeight& lw) {
-    static const Win win = make_window();
-    if (!sums_cleared) HIP_TRY(hipMemsetAsync(sums, 0, sizeof(double) * 2 * (size_t)C, s));
-    // A strip of LH output rows streams LH + 20 input rows: tall strips waste less, but the launch needs a few
-    // workgroups per CU -- as few row strips as still give ~1000 workgroups, at least 64 rows each
-#ifndef SSIM_TARGET_WGS
-#define SSIM_TARGET_WGS 1020
-#endif
-    const int strip = v_render ? FLW : LW;
-    const int per_band = ceil_div(W, strip) * C;
+// The row bands of a launch on C views of H x W pixels.  A strip of LH output rows streams LH + 20 input rows: tall strips
+// waste less -- at least 64 rows each --, but the launch needs a few workgroups per CU.
+enum LossBandKind {
+    LOSS_BANDS_VALUE,       // k_ssim_fwd, k_gt_moments
+    LOSS_BANDS_FUSED_GTM,   // k_ssim_fused with registered moments and no weights
+    LOSS_BANDS_FUSED,       // every other k_ssim_fused
+};
+static int loss_bands(LossBandKind kind, int C, int H, int W) {
+    const int per_band = ceil_div(W, kind == LOSS_BANDS_VALUE ? LW : FLW) * C, tallest = std::max(1, H / 64);
+    // as few row strips as still give ~1000 workgroups
     // (measured, tools/experiments/ssim_bands.sh: ~1000 workgroups, strips of at least 64 rows -- 8 views: 5 bands, 1 view: 17)
-    int bands = std::max(1, std::min(ceil_div(SSIM_TARGET_WGS, per_band), std::max(1, H / 64)));
-    const float2* gtm = v_render ? gt_moments_for(ctx, gt, C, H, W) : nullptr;
+    if (kind == LOSS_BANDS_VALUE) return std::max(1, std::min(ceil_div(1020, per_band), tallest));
     // k_ssim_fused<true> (80 VGPRs) keeps THREE workgroups per CU: as many row bands as still fit the 768 resident slots in
     // one round (round 6, 8 x 1080p: 3 bands = 720 workgroups 0.404 ms, 6 bands 0.403, 4 bands 0.411, the 5 bands of the
     // rule above 0.453, 8 bands 0.437, 10 bands 0.416: what matters is how the workgroups fill whole rounds of the chip)
     // (the same for the kernel that convolves the ground truth itself -- 94 VGPRs, two workgroups per CU, 512 slots: 8 x 1080p
     // with 2 bands 0.436 ms, 3 bands 0.49, 4 bands 0.45, 5 bands 0.47, 6 bands 0.46)
     // (the weighted instantiations -- 89 VGPRs with registered moments, 107 without -- keep two workgroups per CU: 512 slots)
-    if (v_render) bands = std::max(1, std::min((gtm && !lw.weight ? 768 : 512) / std::max(per_band, 1), std::max(1, H / 64)));
+    return std::max(1, std::min((kind == LOSS_BANDS_FUSED_GTM ? 768 : 512) / std::max(per_band, 1), tallest));
+}
+
+// lw.weight != NULL: the weighted loss (file header); sums then has lw.sums_stride doubles per view
+int st3r_loss_impl(st3r_ctx* ctx, hipStream_t s, int C, int H, int W, const float* render, const float* gt,
+                   float w_l1, float w_ssim, double* sums, float* v_render, bool sums_cleared, const LossWeight& lw) {
+    const Win& win = loss_window();
+    if (!sums_cleared) HIP_TRY(hipMemsetAsync(sums, 0, sizeof(double) * 2 * (size_t)C, s));
+    const float* const wgt = lw.weight;
+    const float2* gtm = v_render ? gt_moments_for(ctx, gt, C, H, W) : nullptr;
+    int bands = loss_bands(!v_render ? LOSS_BANDS_VALUE : gtm && !wgt ? LOSS_BANDS_FUSED_GTM : LOSS_BANDS_FUSED, C, H, W);
     if (const char* e = getenv("ST3R_SSIM_BANDS")) bands = std::max(1, atoi(e));   // tuning hook (tools/experiments/ssim_bands.sh)
     const int LH = ceil_div(H, bands);
-    dim3 grid(ceil_div(W, strip), ceil_div(H, LH), C);
-    const float* const wgt = lw.weight;
+    dim3 grid(ceil_div(W, v_render ? FLW : LW), ceil_div(H, LH), C);
     if (!v_render) {   // loss value only
         if (wgt)
             hipLaunchKernelGGL(k_ssim_fwd<true>, grid, dim3(LT), 0, s, LH, H, W, render, gt, win, sums, (float*)nullptr, wgt,
@@ -715,25 +668,18 @@ int st3r_loss_impl(st3r_ctx* ctx, hipStream_t s, int C, int H, int W, const floa
     // (weighted: the kernel forms the constants of every view from w_l1, w_ssim and the view's normalisers)
     const float k_l1 = wgt ? w_l1 : (float)((double)w_l1 / ((double)H * W * 3));
     const float k_ss = wgt ? w_ssim : cnt > 0 ? (float)(-(double)w_ssim / cnt) : 0.f;
-#define SSIM_FUSED_LAUNCH(GTM, WGT)                                                                                        \
-    hipLaunchKernelGGL((k_ssim_fused<GTM, WGT>), grid, dim3(FT2), 0, s, LH, H, W, render, gt, gtm, win, k_l1, k_ss, sums,   \
-                       v_render, wgt, lw.norm, lw.norm_stride, lw.sums_stride)
-    if (gtm) { if (wgt) SSIM_FUSED_LAUNCH(true, true); else SSIM_FUSED_LAUNCH(true, false); }
-    else { if (wgt) SSIM_FUSED_LAUNCH(false, true); else SSIM_FUSED_LAUNCH(false, false); }
-#undef SSIM_FUSED_LAUNCH
-    LAUNCH_CHECK();
+    LAUNCH_BOOL2(k_ssim_fused, gtm != nullptr, wgt != nullptr, grid, dim3(FT2), s, LH, H, W, render, gt, gtm, win, k_l1, k_ss,
+                 sums, v_render, wgt, lw.norm, lw.norm_stride, lw.sums_stride);
     return ST3R_OK;
 }
 
 ST3R_EXPORT int st3r_loss_gt_moments(st3r_ctx* ctx, void* stream, int C, int height, int width, const float* gt,
                                      float* moments) {
     ARG_CHECK(ctx && C > 0 && height > 0 && width > 0 && gt && moments);
-    static const Win win = make_window();
     const int H = height, W = width;
-    const int bands = std::max(1, std::min(ceil_div(1020, ceil_div(W, LW) * C), std::max(1, H / 64)));
-    const int LH = ceil_div(H, bands);
+    const int LH = ceil_div(H, loss_bands(LOSS_BANDS_VALUE, C, H, W));
     hipLaunchKernelGGL(k_gt_moments, dim3(ceil_div(W, LW), ceil_div(H, LH), C), dim3(LT), 0, (hipStream_t)stream, LH, H, W, gt,
-                       win, reinterpret_cast<float2*>(moments));
+                       loss_window(), reinterpret_cast<float2*>(moments));
     LAUNCH_CHECK();
     return ST3R_OK;
 }
@@ -751,7 +697,7 @@ ST3R_EXPORT int st3r_loss_l1_ssim(st3r_ctx* ctx, void* stream, int C, int height
                                   const float* gt, float w_l1, float w_ssim, double* sums, float* v_render) {
     ARG_CHECK(ctx && C > 0 && height > 0 && width > 0 && render && gt && sums);
     return st3r_loss_impl(ctx, (hipStream_t)stream, C, height, width, render, gt, w_l1, w_ssim, sums, v_render, false,
-                          LossWeight{nullptr, nullptr, 0, 2});
+                          LossWeight{});
 }
 
 ST3R_EXPORT int st3r_loss_l1_ssim_weighted(st3r_ctx* ctx, void* stream, int C, int height, int width, const float* render,
@@ -760,7 +706,8 @@ ST3R_EXPORT int st3r_loss_l1_ssim_weighted(st3r_ctx* ctx, void* stream, int C, i
     ARG_CHECK(ctx && C > 0 && height > 0 && width > 0 && render && gt && weight && sums);
     hipStream_t s = (hipStream_t)stream;
     HIP_TRY(hipMemsetAsync(sums, 0, sizeof(double) * 4 * (size_t)C, s));
-    int rc = loss_weight_norms(ctx, s, C, height, width, weight, sums + 2, 4, 1);   // n1, n2 into columns 2 and 3
+    // n1, n2 into columns 2 and 3
+    int rc = st3r_weight_norms(ctx, s, C, height, width, weight, sums + 2, 4, 1, true, SLOT_LWEIGHT_PART);
     if (rc) return rc;
     return st3r_loss_impl(ctx, s, C, height, width, render, gt, w_l1, w_ssim, sums, v_render, true,
                           LossWeight{weight, sums + 2, 4, 4});

@@ -14,32 +14,6 @@
 
 #define DP_MIN_ALPHA 1e-10f
 
-// sum of the weights that count (w > 0) of one chunk
-template <bool VEC>
-__global__ __launch_bounds__(STREAM_T) void k_dprior_wsum(int64_t HW, int64_t chunk, const float* __restrict__ weight,
-                                                          double* __restrict__ part) {
-    __shared__ double red[4];
-    const int c = blockIdx.y;
-    const float* w = weight + (int64_t)c * HW;
-    int64_t lo, hi;
-    stream_chunk(chunk, HW, lo, hi);
-    double acc[1] = {0.0};
-    if (VEC) {
-        for (int64_t i = lo + 4 * (int64_t)threadIdx.x; i < hi; i += 4 * STREAM_T) {
-            const float4 v = *reinterpret_cast<const float4*>(w + i);
-            acc[0] += (double)(v.x > 0.f ? v.x : 0.f); acc[0] += (double)(v.y > 0.f ? v.y : 0.f);
-            acc[0] += (double)(v.z > 0.f ? v.z : 0.f); acc[0] += (double)(v.w > 0.f ? v.w : 0.f);
-        }
-    } else {
-        for (int64_t i = lo + threadIdx.x; i < hi; i += STREAM_T) {
-            const float v = w[i];
-            acc[0] += (double)(v > 0.f ? v : 0.f);
-        }
-    }
-    const double t = block_sum_fixed(acc, red);
-    if (threadIdx.x == 0) part[(int64_t)c * gridDim.x + blockIdx.x] = t;
-}
-
 // one pixel: gradients out, its term of the sum returned
 __device__ __forceinline__ double dp_pixel(float d, float a, float z, float w, float k, float& v_d, float& v_a) {
     v_d = 0.f; v_a = 0.f;
@@ -91,26 +65,35 @@ __global__ __launch_bounds__(STREAM_T) void k_dprior_loss(int64_t HW, int64_t ch
     if (threadIdx.x == 0) part[(int64_t)c * gridDim.x + blockIdx.x] = t;
 }
 
-// workgroups per view and pixels per workgroup: at least four pixels per thread, at most 256 x 8 workgroups in all (one
-// resident round of the chip; the count is C times a per-view count, so it is not an exact multiple of 256)
-void st3r_stream_grid(int C, int64_t HW, int* blocks, int64_t* chunk) {
-    int64_t want = (C * HW + STREAM_ALIGN - 1) / STREAM_ALIGN;
-    if (want > 256 * 8) want = 256 * 8;
-    int64_t b = want / C;
-    if (b < 1) b = 1;
-    int64_t ch = (HW + b - 1) / b;
-    ch = (ch + STREAM_ALIGN - 1) / STREAM_ALIGN * STREAM_ALIGN;
-    *chunk = ch;
-    *blocks = (int)((HW + ch - 1) / ch);
+// out[c * stride] = sum_p w of the C views at `weight` and, interior, out[c * stride + 1] = sum_{p in I} w
+// (k_weight_sums); at_least_one: max(., 1) of each.  slot: the arena slot of the partials.
+int st3r_weight_norms(st3r_ctx* ctx, hipStream_t s, int C, int H, int W, const float* weight, double* out, int stride,
+                      int at_least_one, bool interior, int slot) {
+    const int64_t HW = (int64_t)H * W;
+    int blocks; int64_t chunk;
+    stream_grid(C, HW, &blocks, &chunk);
+    ARENA_GET(slot, double, (size_t)C * blocks * (interior ? 2 : 1), part);
+    LAUNCH_BOOL2(k_weight_sums, HW % 4 == 0 && aligned16(weight), interior, dim3(blocks, C), dim3(STREAM_T), s, HW, chunk,
+                 H, W, weight, part);
+    return interior ? stream_finish<2>(s, C, blocks, part, out, stride, at_least_one)
+                    : stream_finish<1>(s, C, blocks, part, out, stride, at_least_one);
 }
 
-// norm[c * stride] = n_c of the views at `weight`
-static int dp_norms(st3r_ctx* ctx, hipStream_t s, int C, int64_t HW, const float* weight, double* norm, int stride) {
-    int blocks; int64_t chunk;
-    st3r_stream_grid(C, HW, &blocks, &chunk);
-    ARENA_GET(SLOT_DPRIOR_PART, double, (size_t)C * blocks, part);
-    STREAM_LAUNCH(k_dprior_wsum, HW % 4 == 0 && aligned16(weight), blocks, C, s, HW, chunk, weight, part);
-    return stream_finish<1>(s, C, blocks, part, norm, stride, 1);
+// The norms of a registration (those of all its reg.c views, 1 or 2 doubles each, in the arena slot norm_slot), computed
+// by the first call that gets here, on its stream: *valid says that the slot holds this registration's.
+int st3r_registered_weight_norms(st3r_ctx* ctx, hipStream_t s, const ViewReg& reg, const float* weight, int at_least_one,
+                                 bool interior, int part_slot, int norm_slot, int* valid, const double** norms) {
+    const int stride = interior ? 2 : 1;
+    void* p = nullptr; int grown = 0;
+    int rc = st3r_arena_get2(ctx, norm_slot, sizeof(double) * stride * (size_t)reg.c, &p, &grown);
+    if (rc) return rc;
+    if (grown || !*valid) {
+        rc = st3r_weight_norms(ctx, s, reg.c, reg.h, reg.w, weight, (double*)p, stride, at_least_one, interior, part_slot);
+        if (rc) return rc;
+        *valid = 1;
+    }
+    *norms = (const double*)p;
+    return ST3R_OK;
 }
 
 // the pass itself: sums[c * sums_stride] = sum_p w |ED - Z| of view c; norm holds n_c already
@@ -119,7 +102,7 @@ int st3r_depth_prior_loss_impl(st3r_ctx* ctx, hipStream_t s, int C, int H, int W
                                float depth_fac, double* sums, int sums_stride, float* v_depth, float* v_alpha) {
     const int64_t HW = (int64_t)H * W;
     int blocks; int64_t chunk;
-    st3r_stream_grid(C, HW, &blocks, &chunk);
+    stream_grid(C, HW, &blocks, &chunk);
     ARENA_GET(SLOT_DPRIOR_PART, double, (size_t)C * blocks, part);
     STREAM_LAUNCH(k_dprior_loss, HW % 4 == 0 && aligned16(depth, alpha, prior, weight, v_depth, v_alpha), blocks, C, s, HW,
                   chunk, depth, alpha, prior, weight, norm, norm_stride, depth_fac, v_depth, v_alpha, part);
@@ -127,21 +110,16 @@ int st3r_depth_prior_loss_impl(st3r_ctx* ctx, hipStream_t s, int C, int H, int W
 }
 
 // The registered prior that belongs to the C views at `gt` (fused_step.hip): out->prior = NULL if there is none (no
-// registration that applies -- view_reg_first -- or depth_fac == 0).  The n_c of the registration are computed by the
-// first call that gets here, on its stream.
+// registration that applies -- view_reg_first -- or depth_fac == 0).
 int st3r_depth_prior_for(st3r_ctx* ctx, hipStream_t s, const float* gt, int C, int H, int W, DepthPrior* out) {
     *out = DepthPrior{};
     const int64_t c0 = view_reg_first(ctx->dp, gt, C, H, W), HW = (int64_t)H * W;
     if (c0 < 0 || ctx->dp_fac == 0.f) return ST3R_OK;
-    void* p = nullptr; int grown = 0;
-    int rc = st3r_arena_get2(ctx, SLOT_DPRIOR_NORM, sizeof(double) * (size_t)ctx->dp.c, &p, &grown);
+    const double* n_c;
+    int rc = st3r_registered_weight_norms(ctx, s, ctx->dp, ctx->dp_weight, 1, false, SLOT_DPRIOR_PART, SLOT_DPRIOR_NORM,
+                                          &ctx->dp_norm_valid, &n_c);
     if (rc) return rc;
-    if (grown || !ctx->dp_norm_valid) {
-        rc = dp_norms(ctx, s, ctx->dp.c, HW, ctx->dp_weight, (double*)p, 1);
-        if (rc) return rc;
-        ctx->dp_norm_valid = 1;
-    }
-    *out = DepthPrior{ctx->dp_depth + c0 * HW, ctx->dp_weight + c0 * HW, (const double*)p + c0, ctx->dp_fac};
+    *out = DepthPrior{ctx->dp_depth + c0 * HW, ctx->dp_weight + c0 * HW, n_c + c0, ctx->dp_fac};
     return ST3R_OK;
 }
 
@@ -163,7 +141,7 @@ ST3R_EXPORT int st3r_loss_depth_prior(st3r_ctx* ctx, void* stream, int C, int he
     ARG_CHECK(ctx && C > 0 && height > 0 && width > 0);
     ARG_CHECK(depth && alpha && prior && weight && sums && v_depth && v_alpha);
     hipStream_t s = (hipStream_t)stream;
-    int rc = dp_norms(ctx, s, C, (int64_t)height * width, weight, sums + 1, 2);
+    int rc = st3r_weight_norms(ctx, s, C, height, width, weight, sums + 1, 2, 1, false, SLOT_DPRIOR_PART);   // n_c
     if (rc) return rc;
     return st3r_depth_prior_loss_impl(ctx, s, C, height, width, depth, alpha, prior, weight, sums + 1, 2, depth_fac, sums, 2,
                                       v_depth, v_alpha);

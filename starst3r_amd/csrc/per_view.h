@@ -1,5 +1,6 @@
 // What the per-view kernels share: the fixed-order block sum of doubles (gs_pose_bwd.hip, gs_blend_depth.hip and the
-// two files below), the scaffold of the streaming per-view kernels (loss_depth.hip, gs_exposure.hip) and the core of
+// two files below), the scaffold of the streaming per-view kernels (loss_depth.hip, gs_exposure.hip) with the weight
+// sums of both weighted losses (loss_depth.hip, loss.hip), a two-switch kernel launch, and the core of
 // the per-view Adam kernels (gs_pose_step.hip, gs_exposure.hip).  The device helpers are of the form DESIGN.md's "What
 // the projection kernels share" arrives at: references in the order of first use, no arrays by value.
 #pragma once
@@ -38,8 +39,18 @@ __device__ __forceinline__ double block_sum_fixed(double (&v)[NV], double* red) 
 #define STREAM_T 256          // threads per workgroup
 #define STREAM_ALIGN 1024     // chunk granularity in pixels: one 16-byte access per thread
 
-// workgroups per view and pixels per workgroup (defined in loss_depth.hip)
-void st3r_stream_grid(int C, int64_t HW, int* blocks, int64_t* chunk);
+// workgroups per view and pixels per workgroup: at least four pixels per thread, at most 256 x 8 workgroups in all (one
+// resident round of the chip; the count is C times a per-view count, so it is not an exact multiple of 256)
+static inline void stream_grid(int C, int64_t HW, int* blocks, int64_t* chunk) {
+    int64_t want = (C * HW + STREAM_ALIGN - 1) / STREAM_ALIGN;
+    if (want > 256 * 8) want = 256 * 8;
+    int64_t b = want / C;
+    if (b < 1) b = 1;
+    int64_t ch = (HW + b - 1) / b;
+    ch = (ch + STREAM_ALIGN - 1) / STREAM_ALIGN * STREAM_ALIGN;
+    *chunk = ch;
+    *blocks = (int)((HW + ch - 1) / ch);
+}
 
 // every pointer on a 16-byte boundary (NULL counts as aligned)
 template <typename... P>
@@ -50,12 +61,24 @@ __device__ __forceinline__ void stream_chunk(const int64_t& chunk, const int64_t
     lo = (int64_t)blockIdx.x * chunk; hi = min(HW, lo + chunk);
 }
 
-// kernel<true> if vec, else kernel<false>, on the grid of st3r_stream_grid; on failure the enclosing function returns
+// kernel<true> if vec, else kernel<false>, on the grid of stream_grid; on failure the enclosing function returns
 // the error code
 #define STREAM_LAUNCH(kernel, vec, blocks, C, s, ...)                                                           \
     do {                                                                                                        \
         if (vec) hipLaunchKernelGGL(kernel<true>, dim3(blocks, C), dim3(STREAM_T), 0, s, __VA_ARGS__);          \
         else hipLaunchKernelGGL(kernel<false>, dim3(blocks, C), dim3(STREAM_T), 0, s, __VA_ARGS__);             \
+        LAUNCH_CHECK();                                                                                         \
+    } while (0)
+// the same for a kernel with two switches, on any grid: kernel<a, b>
+#define LAUNCH_BOOL2(kernel, a, b, grid, block, s, ...)                                                         \
+    do {                                                                                                        \
+        if (a) {                                                                                                \
+            if (b) hipLaunchKernelGGL((kernel<true, true>), grid, block, 0, s, __VA_ARGS__);                    \
+            else hipLaunchKernelGGL((kernel<true, false>), grid, block, 0, s, __VA_ARGS__);                     \
+        } else {                                                                                                \
+            if (b) hipLaunchKernelGGL((kernel<false, true>), grid, block, 0, s, __VA_ARGS__);                   \
+            else hipLaunchKernelGGL((kernel<false, false>), grid, block, 0, s, __VA_ARGS__);                    \
+        }                                                                                                       \
         LAUNCH_CHECK();                                                                                         \
     } while (0)
 
@@ -83,6 +106,49 @@ static int stream_finish(hipStream_t s, int C, int blocks, const double* part, O
     hipLaunchKernelGGL((k_stream_finish<NV, OUT>), dim3(C), dim3(STREAM_T), 0, s, blocks, part, out, stride, at_least_one);
     LAUNCH_CHECK();
     return ST3R_OK;
+}
+
+// The sums of a per-pixel weight map that normalise a weighted loss (loss_depth.hip, loss.hip): part[(c, workgroup)] =
+// sum_p w of one chunk of view c, the weights that count (w > 0; a negative or NaN weight is 0) in double; INTERIOR: and
+// after it sum_{p in I} w over the interior I of the SSIM term, the pixels WEIGHT_SUM_BORDER away from every edge -- that
+// test needs the pixel's row and column, a division per access, which the plain sum does not pay (H and W: INTERIOR only).
+#define WEIGHT_SUM_BORDER 5   // (loss.hip: HALO)
+template <bool VEC, bool INTERIOR>
+__global__ __launch_bounds__(STREAM_T) void k_weight_sums(int64_t HW, int64_t chunk, int H, int W,
+                                                          const float* __restrict__ weight, double* __restrict__ part) {
+    constexpr int NV = INTERIOR ? 2 : 1, B = WEIGHT_SUM_BORDER;
+    __shared__ double red[4 * NV];
+    const int c = blockIdx.y;
+    const float* w = weight + (int64_t)c * HW;
+    int64_t lo, hi;
+    stream_chunk(chunk, HW, lo, hi);
+    double acc[NV] = {};
+    auto take = [&](int row, int col, float v) {
+        const double d = (double)(v > 0.f ? v : 0.f);
+        acc[0] += d;
+        if constexpr (INTERIOR) {
+            if (row >= B && row < H - B && col >= B && col < W - B) acc[1] += d;
+        }
+    };
+    if (VEC) {
+        for (int64_t i = lo + 4 * (int64_t)threadIdx.x; i < hi; i += 4 * STREAM_T) {
+            const float4 v = *reinterpret_cast<const float4*>(w + i);
+            const float e[4] = {v.x, v.y, v.z, v.w};
+            int row = INTERIOR ? (int)(i / W) : 0, col = INTERIOR ? (int)(i - (int64_t)row * W) : 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                take(row, col, e[k]);
+                if (INTERIOR && ++col == W) { col = 0; ++row; }
+            }
+        }
+    } else {
+        for (int64_t i = lo + threadIdx.x; i < hi; i += STREAM_T) {
+            const int row = INTERIOR ? (int)(i / W) : 0;
+            take(row, INTERIOR ? (int)(i - (int64_t)row * W) : 0, w[i]);
+        }
+    }
+    const double t = block_sum_fixed(acc, red);
+    if (threadIdx.x < NV) part[((int64_t)c * gridDim.x + blockIdx.x) * NV + (NV > 1 ? threadIdx.x : 0)] = t;
 }
 
 // ---- per-view Adam ----

@@ -48,7 +48,7 @@ struct ExposureReg { const float* exposure; float* v_exposure; };
 // the per-pixel loss weights of a set of views (loss.hip); weight == NULL: none apply.  weight [C,H,W]; norm: per view
 // norm_stride doubles, of which the first two are sum_p w and sum_{p in I} w (clamped to >= 1 or not: the readers clamp);
 // sums_stride: doubles per view of the loss kernel's accumulators
-struct LossWeight { const float* weight; const double* norm; int norm_stride; int sums_stride; };
+struct LossWeight { const float* weight = nullptr; const double* norm = nullptr; int norm_stride = 0; int sums_stride = 2; };
 
 // ---- api.hip, fused_step.hip, comm.hip ----
 // The 16 device words next to the fused steps: [0] record count of an asynchronous step (k_adam compares it with the
@@ -118,7 +118,11 @@ int st3r_add_pairs_impl(hipStream_t s, int64_t n_pairs, float* a, const float* b
 int st3r_loss_impl(st3r_ctx* ctx, hipStream_t s, int C, int H, int W, const float* render, const float* gt,
                    float w_l1, float w_ssim, double* sums, float* v_render, bool sums_cleared, const LossWeight& lw);
 int st3r_loss_weight_for(st3r_ctx* ctx, hipStream_t s, const float* gt, int C, int H, int W, LossWeight* out);
-// (st3r_stream_grid, which gs_exposure.hip calls too, is declared with the streaming scaffold in per_view.h)
+// the sums of a weight map that normalise either loss (k_weight_sums, per_view.h), and those of a registration
+int st3r_weight_norms(st3r_ctx* ctx, hipStream_t s, int C, int H, int W, const float* weight, double* out, int stride,
+                      int at_least_one, bool interior, int slot);
+int st3r_registered_weight_norms(st3r_ctx* ctx, hipStream_t s, const ViewReg& reg, const float* weight, int at_least_one,
+                                 bool interior, int part_slot, int norm_slot, int* valid, const double** norms);
 int st3r_depth_prior_for(st3r_ctx* ctx, hipStream_t s, const float* gt, int C, int H, int W, DepthPrior* out);
 int st3r_depth_prior_loss_impl(st3r_ctx* ctx, hipStream_t s, int C, int H, int W, const float* depth, const float* alpha,
                                const float* prior, const float* weight, const double* norm, int norm_stride,

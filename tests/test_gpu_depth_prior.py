@@ -140,6 +140,45 @@ def test_loss_kernel_on_unaligned_buffers(ctx):
         np.testing.assert_allclose(float(sums_o[c, 0]), float(s_ref[c]), rtol=1e-6, atol=1e-6 * zmax * float(n_ref[c]))
 
 
+@pytest.mark.parametrize("shape", [
+    (1, 11, 11),     # odd H * W, one interior pixel
+    (2, 12, 75),     # H * W a multiple of 4: the 16-byte path
+    (2, 50, 37),     # H * W no multiple of 4: view 1 starts off a 16-byte boundary, the 4-byte path
+    (1, 130, 70),    # several workgroups per view, a chunk edge (pixel 1024) inside a row
+    (1, 10, 40),     # no interior: its sum is 0, max(., 1) gives 1
+])
+def test_both_losses_take_their_normalisers_from_one_weight_sum(ctx, shape):
+    """st3r_loss_depth_prior's n_c (sums[:, 1]) and st3r_loss_l1_ssim_weighted's n1 (sums[:, 2]) come from one kernel
+    (k_weight_sums, per_view.h): the same bits for the same map; its n2 (sums[:, 3]) is the same sum over the interior.
+    The weights are multiples of 1/8 in [-1, 2] with a few NaNs: every double sum is exact in any order, so numpy's float64
+    sum of the weights that count (w > 0; negative and NaN weights are 0) is compared with ==."""
+    from starst3r_amd import ops
+    C, H, W = shape
+    rng = np.random.default_rng(100 * H + W)
+    w = (rng.integers(-8, 17, (C, H, W)) / 8.0).astype(np.float32)
+    w.reshape(-1)[rng.choice(w.size, max(2, w.size // 50), replace=False)] = np.nan
+    if C > 1:
+        w[C - 1] = np.minimum(w[C - 1], 0.0)     # a view in which nothing counts (NaNs stay): max(., 1) applies
+    assert np.isnan(w).any() and (w[0] > 0).any() and (w < 0).any()
+    counts = np.where(w > 0, w, np.float32(0)).astype(np.float64)
+    n1_ref = np.maximum(counts.sum((1, 2)), 1.0)
+    n2_ref = np.maximum(counts[:, 5:H - 5, 5:W - 5].sum((1, 2)), 1.0)
+    img = lambda: torch.tensor(rng.random((C, H, W, 3), dtype=np.float32), device="cuda:0")
+    plane = lambda lo: torch.tensor(lo + rng.random((C, H, W, 1), dtype=np.float32), device="cuda:0")
+    wd = torch.tensor(w, device="cuda:0")
+    dsums, _, _ = ops.loss_depth_prior(ctx, plane(0.0), plane(0.25), plane(0.5)[..., 0].contiguous(), wd, DEPTH_FAC)
+    lsums, _ = ops.loss_l1_ssim_weighted(ctx, img(), img(), wd, 0.8, 0.2, want_grad=False)
+    torch.cuda.synchronize()
+    n_c, n1, n2 = dsums[:, 1].cpu(), lsums[:, 2].cpu(), lsums[:, 3].cpu()
+    print(shape, "n_c", n_c.tolist(), "n1", n1.tolist(), "n2", n2.tolist(), "numpy", n1_ref.tolist(), n2_ref.tolist())
+    assert torch.equal(n_c.view(torch.int64), n1.view(torch.int64))
+    assert (n1.numpy() == n1_ref).all() and (n2.numpy() == n2_ref).all()
+    if C > 1:
+        assert float(n1[C - 1]) == 1.0 and float(n2[C - 1]) == 1.0
+    if H <= 10:
+        assert (n2.numpy() == 1.0).all()
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # helpers of the fused-step tests
 # ---------------------------------------------------------------------------------------------------------------------

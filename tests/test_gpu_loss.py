@@ -4,11 +4,9 @@ and k_gt_moments against the float64 oracle, on every launch shape the code dist
 every position of the interior's last column relative to a 64-column strip, several row bands (natural and forced), several
 views with different content; on uniform noise and on images with the structure of real renders (loss_adam_cases.structured).
 
-How st3r_loss_impl picks the row bands (restated here so that a change of the rule shows up as a test to revisit):
-    per_band = ceil(W / 64) * C                       (strips are 64 columns wide in all kernels)
-    k_ssim_fwd, k_gt_moments:  bands = max(1, min(ceil(1020 / per_band), max(1, H // 64)))
-    k_ssim_fused<false>:       bands = max(1, min(512 // per_band, max(1, H // 64)))
-    k_ssim_fused<true>:        bands = max(1, min(768 // per_band, max(1, H // 64)))
+The row bands come from loss_bands() in csrc/loss.hip, the one place that holds the rule (a change there is a reason to
+revisit the shapes here): per kind of kernel, a number of workgroups to reach or of resident slots to fill, divided by
+per_band = ceil(W / 64) * C, and never more than max(1, H // 64) bands.
     ST3R_SSIM_BANDS = n (read on every call) overrides the three loss kernels' count (not k_gt_moments')
     LH = ceil(H / bands) rows per band, ceil(H / LH) bands launched: the last one may be shorter
 Every shape below has per_band <= 6, so all four kernels take max(1, H // 64) bands."""
