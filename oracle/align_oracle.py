@@ -143,6 +143,37 @@ def loss_dust3r(pb, cam2w, pts, gamma=1.1):             # reconstruct.py:311-323
     return (pb.dust_conf @ gamma_rho(d, gamma)) / pb.dust_conf.sum()
 
 
+def loss_and_grads(flat, params, stage, dtype=torch.float64, core=None, loss_dust3r_w=0.01, gamma=None, gammad=1.1):
+    """One evaluation at given parameters (and, optionally, given NORMALISED core depths), in `dtype`, with torch
+    autograd: -> dict(loss, grads {pps, log_focals, quats, trans, log_sizes, core_depth}, intrinsics, cam2w, w2cam,
+    depthmaps, pts3d), all numpy.  Gradients are taken with respect to every parameter, whatever the stage trains (the parity
+    tests of tests/align_cases.py pick the trainable ones)."""
+    pb = Problem(flat, dtype)
+    if core is not None:
+        pb.core = torch.as_tensor(np.asarray(core), dtype=dtype).clone()
+    p = init_params(pb, params)
+    for v in p.values():
+        v.requires_grad_(True)
+    pb.core = pb.core.clone().requires_grad_(True)
+    K, w2cam, cam2w, depth = make_K_cam_depth(pb, p)
+    pts = make_pts3d(pb, K, cam2w, depth)
+    gamma = (1.1 if stage == 1 else 0.4) if gamma is None else gamma
+    main = loss_3d(pb, pts, gamma) if stage == 1 else loss_2d(pb, K, w2cam, pts, gamma)
+    loss = main + loss_dust3r_w * loss_dust3r(pb, cam2w, pts, gammad)
+    grads = {k: np.zeros(tuple(v.shape)) for k, v in p.items()}
+    grads["core_depth"] = np.zeros(tuple(pb.core.shape))
+    if loss.requires_grad:
+        loss.backward()
+        for k, v in p.items():
+            if v.grad is not None:
+                grads[k] = v.grad.numpy().copy()
+        if pb.core.grad is not None:
+            grads["core_depth"] = pb.core.grad.numpy().copy()
+    n = lambda t: t.detach().numpy().copy()
+    return dict(loss=float(loss.detach()), grads=grads, intrinsics=n(K), cam2w=n(cam2w), depthmaps=n(depth), pts3d=n(pts),
+                w2cam=n(w2cam))
+
+
 def cosine_schedule(alpha, lr_base, lr_end=0.0):
     return lr_end + (lr_base - lr_end) * (1 + np.cos(alpha * np.pi)) / 2
 

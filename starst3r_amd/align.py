@@ -58,6 +58,9 @@ def run(flat, lr1=0.07, niter1=500, lr2=0.014, niter2=200, prev_params=None, los
     dust_a1, dust_tgt, dust_img2 = i32(flat["dust_a1"]), f32(flat["dust_tgt"]), i32(flat["dust_img2"])
     dust_w = weights(flat["dust_conf"])
     edges = i32(np.asarray(flat["mst_edges"]).reshape(-1, 2))
+    n_edges = edges.shape[0]
+    if n_edges == 0:   # one view: the library wants a pointer even to no edges (an empty tensor has none)
+        edges = i32(np.zeros((1, 2)))
 
     # parameters (reconstruct.py:150-152, 170, 200-201, 277); warm start splices the first n views (:408-415)
     P = dict(pps=(f32(flat["pps"]) / imsizes).contiguous(), log_focals=base_focals.log().contiguous(),
@@ -112,7 +115,7 @@ def run(flat, lr1=0.07, niter1=500, lr2=0.014, niter2=200, prev_params=None, los
         corr_a1.numel(), p(corr_a1, torch.int32), p(corr_a2, torch.int32), p(corr_w),
         c2d_a2.numel(), p(c2d_pix), p(c2d_a2, torch.int32), p(c2d_img1, torch.int32), p(c2d_w),
         dust_a1.numel(), p(dust_a1, torch.int32), p(dust_tgt), p(dust_img2, torch.int32), p(dust_w),
-        int(flat["mst_root"]), edges.shape[0], p(edges, torch.int32), lr1, niter1, lr2, niter2, loss_dust3r_w,
+        int(flat["mst_root"]), n_edges, p(edges, torch.int32), lr1, niter1, lr2, niter2, loss_dust3r_w,
         p(P["pps"]), p(P["log_focals"]), p(P["quats"]), p(P["trans"]), p(P["log_sizes"]),
         p(work), work.numel(), p(cam), p(pts), p(losses),
         lr_host.ctypes.data if lr_host is not None else None, float(gamma1), float(gamma2), float(gammad), int(bool(opt_pp)),
@@ -130,6 +133,7 @@ def run(flat, lr1=0.07, niter1=500, lr2=0.014, niter2=200, prev_params=None, los
                # depthmaps the reference unprojects from; the stepped core depths are params["core_depth"])
                _cam_rows=cam, _core=core_res, _base_focals=base_focals,
                _adam_m=work[:11 * Cn].clone(),  # first moments, order pps|log_focals|quats|trans|log_sizes (tests)
+               _adam_v=work[11 * Cn:22 * Cn].clone(),  # second moments, same order (tests)
                _flags=work[22 * Cn + 24 * Cn + 20 * Cn:22 * Cn + 24 * Cn + 20 * Cn + 4].clone())  # loss, NaN stop
     if depth_work is not None:   # opt_depth: first moments of the core depths [C, G] (tests)
         n_rows2 = depth_work.numel() - 3 * Cn * G

@@ -451,6 +451,10 @@ __device__ __forceinline__ void align_update_body(const AlignProblem& P, const A
     for (int k = i; k < 2 * P.n_edges; k += blockDim.x) sedge[k] = P.edges[k];
     float* flags = S.acc + C * ACC_STRIDE;
     if (U.do_backward && *(flags + 1) != 0.f) return;  // stopped earlier by a NaN loss
+    // every wave has read the flag before thread 0 may set it below: without this barrier nothing orders that write
+    // after another wave's read when n_part < 0 (the first barrier used to sit inside the branch that follows), and a
+    // late wave could return while the others wait at the next barrier
+    __syncthreads();
     if (U.do_backward && U.n_part >= 0) {   // gradient sums and loss = the residual workgroups' partials, added in
                                             // workgroup order (n_part < 0: k_align_reduce has done it)
         const int nacc = C * ACC_STRIDE + 1;
@@ -767,7 +771,7 @@ ST3R_EXPORT int st3r_align_run_opts(st3r_ctx* ctx, void* stream, int C, int G, i
     };
     HIP_TRY(hipMemsetAsync(work, 0, sizeof(float) * (size_t)need, s));
     const size_t sh = sizeof(float) * (4 * ((size_t)C * ACC_STRIDE + 1) + (size_t)C * CAM_STRIDE);
-    if (sh > 64 * 1024)   // more than ~190 views: the four accumulator copies pass the default dynamic-LDS limit
+    if (sh > 64 * 1024)   // 416 C + 16 bytes: from 158 views on (157 still fit) the default dynamic-LDS limit is passed
         HIP_TRY(hipFuncSetAttribute((const void*)k_align_resid, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
     // one residual workgroup per 256 rows up to 1024 workgroups (then `rpt` groups of 256 rows each); up to 32 partials
     // are added by k_align_update itself, more by k_align_reduce (one thread per accumulator word)
