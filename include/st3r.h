@@ -718,6 +718,10 @@ int st3r_focal_weiszfeld(st3r_ctx* ctx, void* stream, int H, int W, const float*
 /* the same for n_views images of one size in ONE launch: canon [n_views,H,W,3] -> focal_out [n_views] */
 int st3r_focal_weiszfeld_batch(st3r_ctx* ctx, void* stream, int n_views, int H, int W, const float* canon, float ppx,
                                float ppy, float min_focal, float max_focal, float* focal_out);
+/* The number of workgroups per view, *G, that st3r_focal_weiszfeld_batch launches for n_views (1..1024) images of
+ * H x W on the context's device (it depends on how many workgroups that device holds at once).  Host arithmetic and one
+ * occupancy query, no launch: it is here so that tests can assert which barrier shapes their inputs reach. */
+int st3r_focal_plan(st3r_ctx* ctx, int n_views, int H, int W, int* G);
 int st3r_anchor_offsets(st3r_ctx* ctx, void* stream, int64_t n, int H, int W, int subsample, const float* canon2,
                         const float* xy, int32_t* idx_out, float* off_out);
 

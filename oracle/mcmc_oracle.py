@@ -94,7 +94,11 @@ def compute_relocation(o, s, ratio, binoms=None):
         denom = np.float32(0)
         for i in range(1, n_idx + 1):
             for k in range(i):
-                term = np.float32((-1.0) ** k / math.sqrt(k + 1)) * np.power(no, np.float32(k + 1), dtype=np.float32)
+                # float32 square root and division, so that this matches the kernel's sqrtf and division (a double-precision
+                # 1 / sqrt rounded once differs in the last bit for k + 1 = 6, 7, 17, 18, 21, 24, 28, 34, 39); the
+                # product and the sum below are rounded separately, which the kernel does too (contraction off there)
+                coef = np.float32((-1.0) ** k) / np.sqrt(np.float32(k + 1))
+                term = coef * np.power(no, np.float32(k + 1), dtype=np.float32)
                 denom = np.float32(denom + binoms[i - 1, k] * term)
         new_o[j] = no
         new_s[j] = (o[j] / denom) * s[j]

@@ -170,12 +170,8 @@ ST3R_EXPORT int st3r_canon_view(st3r_ctx* ctx, void* stream, int n, int H, int W
     return ST3R_OK;
 }
 
-ST3R_EXPORT int st3r_focal_weiszfeld_batch(st3r_ctx* ctx, void* stream, int n_views, int H, int W, const float* canon,
-                                           float ppx, float ppy, float min_focal, float max_focal, float* focal_out) {
-    ARG_CHECK(ctx && n_views > 0 && n_views <= 1024 && H > 0 && W > 0 && canon && focal_out && min_focal > 0.f &&
-              max_focal >= min_focal);
-    hipStream_t s = (hipStream_t)stream;
-    // G workgroups per view: enough to spread an image over many CUs, few enough that the whole grid is resident
+// G workgroups per view: enough to spread an image over many CUs, few enough that the whole grid is resident
+static int focal_plan(st3r_ctx* ctx, int n_views, int H, int W) {
     int G = min(FB_MAX_G, max(1, 1024 / n_views));
     G = min(G, max(1, ceil_div((int64_t)H * W, FB_THREADS)));
     // the per-view counter barrier needs every workgroup of the grid resident at once: bound the grid by what THIS
@@ -188,6 +184,21 @@ ST3R_EXPORT int st3r_focal_weiszfeld_batch(st3r_ctx* ctx, void* stream, int n_vi
         const int64_t resident = (e1 == hipSuccess && e2 == hipSuccess) ? (int64_t)per_cu * cus / 2 : 0;   // half: other streams
         if (resident < (int64_t)G * n_views) G = (int)max((int64_t)1, resident / n_views);
     }
+    return G;
+}
+
+ST3R_EXPORT int st3r_focal_plan(st3r_ctx* ctx, int n_views, int H, int W, int* G) {
+    ARG_CHECK(ctx && n_views > 0 && n_views <= 1024 && H > 0 && W > 0 && G);
+    *G = focal_plan(ctx, n_views, H, W);
+    return ST3R_OK;
+}
+
+ST3R_EXPORT int st3r_focal_weiszfeld_batch(st3r_ctx* ctx, void* stream, int n_views, int H, int W, const float* canon,
+                                           float ppx, float ppy, float min_focal, float max_focal, float* focal_out) {
+    ARG_CHECK(ctx && n_views > 0 && n_views <= 1024 && H > 0 && W > 0 && canon && focal_out && min_focal > 0.f &&
+              max_focal >= min_focal);
+    hipStream_t s = (hipStream_t)stream;
+    const int G = focal_plan(ctx, n_views, H, W);
     const size_t part_bytes = sizeof(unsigned long long) * 11 * (size_t)n_views * G;
     const size_t cnt_off = (part_bytes + 255) & ~(size_t)255;
     void* p;

@@ -113,9 +113,14 @@ __global__ __launch_bounds__(256) void k_mcmc_update_sources(int N, const uint32
     float denom = 0.0f;
     for (int i = 1; i <= n_idx; ++i) {
         for (int k = 0; k < i; ++k) {
+            // product and sum rounded separately (contraction off: v_mul_f32 + v_add_f32, no v_fmac_f32), in the order
+            // of the float32 reference: where the alternating sum has lost every digit (sigmoid == 1.0f, ratio > 24,
+            // DESIGN.md) its sign decides between a finite and a NaN scale, and a fused sum decides differently from
+            // the reference at ratios 32, 47, 49, 50
+#pragma clang fp contract(off)
             const float sgn = (k & 1) ? -1.0f : 1.0f;
             const float term = (sgn / sqrtf((float)(k + 1))) * powf(new_o, (float)(k + 1));
-            denom += binoms[(i - 1) * MCMC_NMAX + k] * term;
+            denom = denom + binoms[(i - 1) * MCMC_NMAX + k] * term;
         }
     }
     const float coeff = o / denom;

@@ -551,6 +551,13 @@ def focal_weiszfeld_batch(ctx, canons, pp, min_focal=0.5, max_focal=3.5):
     return out
 
 
+def focal_plan(ctx, n_views, H, W):
+    """Workgroups per view that focal_weiszfeld_batch launches for n_views images of H x W on this device."""
+    G = C.c_int(0)
+    _lib.check(_lib.lib().st3r_focal_plan(ctx.handle, n_views, H, W, C.byref(G)))
+    return G.value
+
+
 def anchor_offsets(ctx, canon2, xy, subsample):
     """Mast3r anchor_depth_offsets [U] for one list of correspondence pixels xy [n,2] -> (idx int32 [n], off [n])."""
     H, W = canon2.shape
