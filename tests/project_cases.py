@@ -184,11 +184,13 @@ def reg_grads(case):
     return rv * of / case.N * sg * (1.0 - sg), rv * sf / (3.0 * case.N) * np.exp(case.scales.astype(np.float64))
 
 
-def ref64(case, vis, v_splats, reg=True, campos=None):
+def ref64(case, vis, v_splats, reg=True, campos=None, cameras=False):
     """float64 torch autograd through oracle.gs_torch_ref.project / sh_color (which hold the clamp as minimum / maximum and
     the colour clamp_min), jointly into means, quats, scales, opacities and sh; visibility is given (the C oracle's or the
     kernel's radii, as in test_gpu_pose_grad.chain_ref); the culled pairs' cotangents are never touched; campos: the float32
-    camera positions the kernel was given, if not the oracle's"""
+    camera positions the kernel was given, if not the oracle's.  cameras: also into the view matrices ("viewmats" [Cn, 4, 4],
+    with campos = inverse(V)[:3, 3] INSIDE the graph, whatever `campos` says) and the intrinsics ("Ks4" [Cn, 4]: fx, fy, cx,
+    cy, the clamp limits' dependence on them included) -- tests/per_view_kernel_cases.py"""
     import torch
     from oracle import gs_torch_ref as tr
     N, Cn = case.N, case.Cn
@@ -199,7 +201,16 @@ def ref64(case, vis, v_splats, reg=True, campos=None):
     for p in P:
         p.requires_grad_()
     means, quats, scales, opac, sh = P
-    vm, K, campos = t(case.viewmats), t(case.Ks), t(case.campos() if campos is None else campos)
+    vm, K = t(case.viewmats), t(case.Ks)
+    if cameras:
+        k4 = torch.stack([K[:, 0, 0], K[:, 1, 1], K[:, 0, 2], K[:, 1, 2]], 1).clone().requires_grad_()
+        vm.requires_grad_()
+        o, l = torch.zeros(Cn, dtype=torch.float64), torch.ones(Cn, dtype=torch.float64)
+        K = torch.stack([k4[:, 0], o, k4[:, 2], o, k4[:, 1], k4[:, 3], o, o, l], 1).reshape(Cn, 3, 3)
+        campos = torch.inverse(vm)[:, :3, 3]
+        P = P + [vm, k4]
+    else:
+        campos = t(case.campos() if campos is None else campos)
     outs, cots = [], []
     for c in range(Cn):
         idx = torch.tensor(np.nonzero(vis[c])[0])
@@ -214,7 +225,7 @@ def ref64(case, vis, v_splats, reg=True, campos=None):
         G = [np.zeros(tuple(p.shape)) if g is None else g.numpy() for g, p in zip(G, P)]
     else:
         G = [np.zeros(tuple(p.shape)) for p in P]
-    out = dict(zip(GROUPS, G))
+    out = dict(zip(GROUPS + ("viewmats", "Ks4"), G))
     if reg:
         go_, gs_ = reg_grads(case)
         out["opacities"] = out["opacities"] + go_; out["scales"] = out["scales"] + gs_
