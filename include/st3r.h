@@ -321,6 +321,56 @@ int st3r_exposure_adam_step(st3r_ctx* ctx, void* stream, int C, float* exposure,
 int st3r_ctx_set_exposure(st3r_ctx* ctx, const float* gt, const float* exposure, float* v_exposure, int C, int height,
                           int width);
 
+/* Backgrounds and alpha supervision.  rgb, out, v_out [C,H,W,3]; alpha, v_alpha_in, v_alpha [C,H,W,1]; backgrounds,
+ * v_backgrounds [C,3]; target, weight [C,H,W]; all float32.
+ * st3r_composite_fwd: the render over a background colour per view (`backgrounds` of gsplat.rasterization); per pixel
+ * and channel, in float32,
+ *   y_j = fmaf(1 - a, b_j, x_j)                                  (out may equal rgb)
+ * st3r_alpha_grad: everything that flows into d loss / d alpha besides the depth prior, in one pass over the pixels.
+ *   background term (backgrounds and v_out given; v_out = d loss / d y, which is d loss / d x as well: not written):
+ *     t_bg = -fmaf(b_2, v_2, fmaf(b_1, v_1, b_0 * v_0))
+ *     v_backgrounds (may be NULL; written whole): v_b[c][j] = sum_p (1 - a) v_j -- the float32 factor 1 - a, products
+ *     and sums in double, stored as float32
+ *   alpha term (target, weight and sums given; alpha_fac finite): a weighted L1 between alpha and the target M,
+ *     n_c = max(sum_p w, 1)     loss_c = alpha_fac * sum_p w |a - M| / n_c
+ *     t_a = k w sign(a - M),  k = (float)((double)alpha_fac / n_c),  sign(0) = 0
+ *     sums [C,2] (double, device; written): per view  sum_p w |a - M|  and  n_c
+ *     A pixel with w <= 0 or a NaN weight contributes nothing and gets t_a = 0 whatever M holds there (NaN, inf).
+ *   v_alpha = ((v_alpha_in or 0) + t_bg) + t_a, in that order, an absent term being +0; v_alpha may equal v_alpha_in.
+ * A term is given whole or not at all, and at least one of the two: otherwise ST3R_ERR_INVALID.  The kernel is
+ * instantiated per combination (background term, alpha term, accumulate, 16-byte / 4-byte accesses), so a call loads
+ * only what it uses.  Sums in double in a fixed order (per thread, wave butterfly, the four waves in order, one partial
+ * per (view, workgroup), a finishing launch), no atomics: the same inputs give the same bits.  16-byte accesses when
+ * H * W is a multiple of 4 and the image pointers are 16-byte aligned, 4-byte accesses otherwise. */
+int st3r_composite_fwd(st3r_ctx* ctx, void* stream, int C, int height, int width, const float* rgb, const float* alpha,
+                       const float* backgrounds, float* out);
+int st3r_alpha_grad(st3r_ctx* ctx, void* stream, int C, int height, int width, const float* alpha,
+                    const float* backgrounds, const float* v_out, const float* target, const float* weight,
+                    float alpha_fac, const float* v_alpha_in, double* sums, float* v_alpha, float* v_backgrounds);
+
+/* Registers the backgrounds [C,3] of the images at `gt` [C,H,W,3].  From then on st3r_gs_train_fwd_bwd / _step /
+ * _step_poses compare the composited render with the ground truth whenever their ground-truth pointer is `gt` or a
+ * whole-view offset into it (view chunks) with the same height and width: blend forward, st3r_composite_fwd into scratch
+ * of its own (the raw render stays where st3r_ctx_peek(8) finds it), exposure forward on the composite (scene first,
+ * then camera), the loss, exposure backward, the depth prior's loss, st3r_alpha_grad -- which writes d loss / d alpha, or
+ * adds to the depth prior's --, blend backward with that v_alpha: the kernels and the order of the unfused chain, so the
+ * same bits.  The backgrounds are fixed: no gradient for them is formed.  Every other registration combines with it.
+ * With no registration every call runs exactly the launches it ran before.  The buffer stays the CALLER's; gt = NULL
+ * or backgrounds = NULL clears the registration.  st3r_gs_raster_train ignores it; with a communicator attached the
+ * training calls return ST3R_ERR_INVALID while a registration applies. */
+int st3r_ctx_set_background(st3r_ctx* ctx, const float* gt, const float* backgrounds, int C, int height, int width);
+
+/* Registers alpha targets for the images at `gt` [C,H,W,3]: target, weight [C,H,W] as above.  From then on the training
+ * calls add the alpha term above to their loss whenever their ground-truth pointer is `gt` or a whole-view offset into
+ * it with the same height and width and alpha_fac != 0: st3r_alpha_grad behind the depth prior's loss (see
+ * st3r_ctx_set_background), loss_out includes sum_c loss_c.  The rules of st3r_ctx_set_depth_prior: n_c is computed once
+ * per registration, by the first call that uses it and on that call's stream; with no registration, or alpha_fac == 0,
+ * every call runs exactly the launches it ran before; the buffers stay the CALLER's and must stay unchanged while
+ * registered; gt = NULL (or target / weight = NULL) clears the registration; st3r_gs_raster_train ignores it; with a
+ * communicator attached the training calls return ST3R_ERR_INVALID while targets apply. */
+int st3r_ctx_set_alpha_target(st3r_ctx* ctx, const float* gt, const float* target, const float* weight, int C, int height,
+                              int width, float alpha_fac);
+
 /* Gradient of the render loss with respect to each camera's intrinsics, from the per-pair gradients v_splats of
  * st3r_gs_blend_bwd (floats 0-1 and 3-5; colour and depth do not depend on K): v_Ks [C,4] = d loss / d (fx, fy, cx, cy),
  * written whole.  Per visible pair (radius > 0), in float32, with p = R m + t = (x, y, z), the projection Jacobian

@@ -92,6 +92,11 @@ enum ArenaSlot {
     SLOT_KGRAD_PART,  // intrinsics backward (gs_intrinsics.hip): one 4-double partial per (camera, block of 256 Gaussians)
     SLOT_LWEIGHT_PART, // per-pixel loss weights (loss.hip): one 2-double partial per (view, workgroup) of their sums
     SLOT_LWEIGHT_NORM, // the same: (sum_p w, sum_{p in I} w) of every registered view, computed once per registration
+    SLOT_COMPOSITE,   // fused step with backgrounds (fused_step.hip): the composited image [C,H,W,3] the exposure / the loss reads (SLOT_RGB keeps the raw render)
+    SLOT_AGRAD_PART,  // st3r_alpha_grad (gs_alpha.hip): per (view, workgroup) three doubles (v_backgrounds), then one (sum w |a - M|)
+    SLOT_ATARGET_PART, // alpha targets (gs_alpha.hip): one double partial per (view, workgroup) of the weights' sums
+    SLOT_ATARGET_NORM, // the same: n_c = max(sum w_c, 1) of every registered view, computed once per registration
+    SLOT_ATARGET_SUMS, // the same: sum_p w |a - M| per view of the fused step
     SLOT_COUNT
 };
 
@@ -170,6 +175,11 @@ struct st3r_ctx {
     // per-pixel loss weights (st3r_ctx_set_loss_weight, loss.hip); lw_norm_valid: SLOT_LWEIGHT_NORM holds the sums of this
     // registration (computed by the first training call that uses it)
     ViewReg lw; const float* lw_weight; int lw_norm_valid;
+    // backgrounds (st3r_ctx_set_background, gs_alpha.hip): [c,3]
+    ViewReg bg; const float* bg_colors;
+    // alpha targets (st3r_ctx_set_alpha_target, gs_alpha.hip); at_fac == 0: none; at_norm_valid: SLOT_ATARGET_NORM holds
+    // the n_c of this registration (computed by the first training call that uses it)
+    ViewReg at; const float* at_target; const float* at_weight; float at_fac; int at_norm_valid;
     int bwd_stamp;  // generation stamp of the per-(record, tile) partial-gradient slots
     int depth_stamp;  // the same for the depth backward's slots (SLOT_VTILE_DEPTH)
     uint32_t scan_gen;   // single-pass scan (gs_isect.hip): generation of its status words

@@ -222,7 +222,8 @@ __global__ void k_finalize_loss(int C, const double* __restrict__ sums, const do
                                 double inv_px, double inv_cnt, double w_l1, double w_ssim, double reg_views,
                                 double opac_k, double scale_k, float* __restrict__ loss_out,
                                 const double* __restrict__ dsums, const double* __restrict__ dnorm, double depth_fac,
-                                const double* __restrict__ wnorm) {
+                                const double* __restrict__ wnorm, const double* __restrict__ asums,
+                                const double* __restrict__ anorm, double alpha_fac) {
     if (threadIdx.x == 0 && blockIdx.x == 0) {
         double loss = 0;
         if (wnorm)   // per-pixel weights (loss.hip): wnorm[2c], wnorm[2c + 1] = sum_p w, sum_{p in I} w of view c
@@ -234,20 +235,24 @@ __global__ void k_finalize_loss(int C, const double* __restrict__ sums, const do
         loss += reg_views * (opac_k * reg_sums[0] + scale_k * reg_sums[1]);
         if (dsums)   // depth prior (loss_depth.hip): depth_fac sum_p w |ED - Z| / n_c per view
             for (int c = 0; c < C; ++c) loss += depth_fac * dsums[c] / dnorm[c];
+        if (asums)   // alpha targets (gs_alpha.hip): alpha_fac sum_p w |a - M| / n_c per view
+            for (int c = 0; c < C; ++c) loss += alpha_fac * asums[c] / anorm[c];
         loss_out[0] = (float)loss;
     }
 }
 
 // the per-view sums of a step -> its loss; dp_sums == NULL: no depth term; lw.weight != NULL: the weighted loss, normalised
-// by the sums of the views' weights
+// by the sums of the views' weights; at_sums == NULL: no alpha term
 static int finalize_loss(hipStream_t s, int C, int H, int W, const double* sums, const double* reg_sums, float ssim_fac,
                          double reg_views, double opac_k, double scale_k, float* loss_out, const double* dp_sums,
-                         const DepthPrior& dp, const LossWeight& lw) {
+                         const DepthPrior& dp, const LossWeight& lw, const double* at_sums = nullptr,
+                         const AlphaTarget& at = AlphaTarget{}) {
     const int Hi = H - 10, Wi = W - 10;
     const double cnt = (Hi > 0 && Wi > 0) ? (double)Hi * Wi * 3 : 0.0;
     hipLaunchKernelGGL(k_finalize_loss, dim3(1), dim3(64), 0, s, C, sums, reg_sums, 1.0 / ((double)H * W * 3),
                        cnt > 0 ? 1.0 / cnt : 0.0, (double)(1.0f - ssim_fac), (double)ssim_fac, reg_views, opac_k, scale_k,
-                       loss_out, dp_sums, dp.norm, (double)dp.fac, lw.weight ? lw.norm : nullptr);
+                       loss_out, dp_sums, dp.norm, (double)dp.fac, lw.weight ? lw.norm : nullptr, at_sums, at.norm,
+                       (double)at.fac);
     LAUNCH_CHECK();
     return ST3R_OK;
 }
@@ -264,31 +269,43 @@ struct ViewBatch {
     float* v_viewmats;    // [C,4,4]
     bool exposure;        // exposures may be registered for these views (st3r_ctx_set_exposure)
     bool weighted;        // per-pixel loss weights may be registered for these views (st3r_ctx_set_loss_weight)
+    bool background;      // backgrounds may be registered for these views (st3r_ctx_set_background)
+    double* at_sums;      // [C]: sum_p w |a - M| (st3r_ctx_set_alpha_target); NULL: no alpha targets
     ViewBatch slice(int c0, int c1) const {
         return {v.slice(c0, c1), gt + (int64_t)c0 * v.H * v.W * 3, sums + 2 * c0, dp_sums ? dp_sums + c0 : nullptr,
-                v_viewmats ? v_viewmats + 16 * c0 : nullptr, exposure, weighted};
+                v_viewmats ? v_viewmats + 16 * c0 : nullptr, exposure, weighted, background,
+                at_sums ? at_sums + c0 : nullptr};
     }
 };
 
-// the images of a step, in ctx scratch (depth, v_depth, v_alpha: with a depth prior only; exposed: with exposures only)
-struct StepImages { float *rgb, *alpha; int32_t* last; float *v_rgb, *depth, *v_depth, *v_alpha, *exposed; };
+// the images of a step, in ctx scratch (depth, v_depth: with a depth prior only; v_alpha: with a depth prior, backgrounds
+// or alpha targets; exposed: with exposures only; composite: with backgrounds only)
+struct StepImages { float *rgb, *alpha; int32_t* last; float *v_rgb, *depth, *v_depth, *v_alpha, *exposed, *composite; };
 
-static int step_images(st3r_ctx* ctx, const RasterOut& ro, bool with_depth, bool with_exposure, StepImages* im) {
+static int step_images(st3r_ctx* ctx, const RasterOut& ro, bool with_depth, bool with_exposure, bool with_background,
+                       bool with_v_alpha, StepImages* im) {
     const int64_t n_px = (int64_t)ro.C * ro.H * ro.W;
     ARENA_GET(SLOT_RGB, float, n_px * 3, rgb);
     ARENA_GET(SLOT_ALPHA, float, n_px, alpha);
     ARENA_GET(SLOT_LAST, int32_t, n_px, last);
     ARENA_GET(SLOT_VRENDER, float, n_px * 3, v_rgb);
-    *im = StepImages{rgb, alpha, last, v_rgb, nullptr, nullptr, nullptr, nullptr};
+    *im = StepImages{rgb, alpha, last, v_rgb, nullptr, nullptr, nullptr, nullptr, nullptr};
     if (with_exposure) {
         ARENA_GET(SLOT_EXPOSED, float, n_px * 3, exposed);
         im->exposed = exposed;
     }
+    if (with_background) {
+        ARENA_GET(SLOT_COMPOSITE, float, n_px * 3, composite);
+        im->composite = composite;
+    }
     if (with_depth) {
         ARENA_GET(SLOT_DEPTH, float, n_px, depth);
         ARENA_GET(SLOT_VDEPTH, float, n_px, v_depth);
+        im->depth = depth; im->v_depth = v_depth;
+    }
+    if (with_depth || with_v_alpha) {
         ARENA_GET(SLOT_VALPHA, float, n_px, v_alpha);
-        im->depth = depth; im->v_depth = v_depth; im->v_alpha = v_alpha;
+        im->v_alpha = v_alpha;
     }
     return ST3R_OK;
 }
@@ -298,7 +315,11 @@ static int step_images(st3r_ctx* ctx, const RasterOut& ro, bool with_depth, bool
 // and v_alpha back.
 static int forward_and_losses(st3r_ctx* ctx, hipStream_t s, const RasterOut& ro, const ViewBatch& b, float ssim_fac,
                               bool sums_cleared, const DepthPrior& dp, const ExposureReg& ex, const LossWeight& lw,
-                              const StepImages& im) {
+                              const StepImages& im, const Background& bg = Background{},
+                              const AlphaTarget& at = AlphaTarget{}) {
+    // bg.colors != NULL: the loss sees the render composited over the views' backgrounds (st3r_composite_fwd, into scratch
+    // of its own, before the exposure: scene first, then camera); at.target != NULL: the alpha term.  Either one sends a
+    // v_alpha back (st3r_alpha_grad, behind the depth prior, onto whose v_alpha it accumulates)
     // ex.exposure != NULL: the loss compares y = E x with the ground truth (the stand-alone kernels of gs_exposure.hip, in
     // the order of the unfused chain); im.v_rgb leaves as d loss / d x, ex.v_exposure as d loss / d E of these views
     // lw.weight != NULL: the photometric loss takes the views' per-pixel weights (on y with exposures, whose backward then
@@ -310,15 +331,24 @@ static int forward_and_losses(st3r_ctx* ctx, hipStream_t s, const RasterOut& ro,
     st3r_prof_end(ctx, s, STG_BLEND_FWD);
     if (rc) return rc;
     st3r_prof_begin(ctx, s, STG_LOSS);
-    if (ex.exposure) rc = st3r_exposure_fwd_impl(s, ro.C, ro.H, ro.W, im.rgb, ex.exposure, im.exposed);
+    const float* x = im.rgb;   // what the camera sees: the render, or the render over its background
+    if (bg.colors) {
+        rc = st3r_composite_fwd_impl(s, ro.C, ro.H, ro.W, im.rgb, im.alpha, bg.colors, im.composite);
+        x = im.composite;
+    }
+    if (!rc && ex.exposure) rc = st3r_exposure_fwd_impl(s, ro.C, ro.H, ro.W, x, ex.exposure, im.exposed);
     if (!rc)
-        rc = st3r_loss_impl(ctx, s, ro.C, ro.H, ro.W, ex.exposure ? im.exposed : im.rgb, b.gt, 1.0f - ssim_fac, ssim_fac,
+        rc = st3r_loss_impl(ctx, s, ro.C, ro.H, ro.W, ex.exposure ? im.exposed : x, b.gt, 1.0f - ssim_fac, ssim_fac,
                             b.sums, im.v_rgb, sums_cleared, lw);
     if (!rc && ex.exposure)
-        rc = st3r_exposure_bwd_impl(ctx, s, ro.C, ro.H, ro.W, im.rgb, ex.exposure, im.v_rgb, im.v_rgb, ex.v_exposure);
+        rc = st3r_exposure_bwd_impl(ctx, s, ro.C, ro.H, ro.W, x, ex.exposure, im.v_rgb, im.v_rgb, ex.v_exposure);
     if (!rc && dp.prior)
         rc = st3r_depth_prior_loss_impl(ctx, s, ro.C, ro.H, ro.W, im.depth, im.alpha, dp.prior, dp.weight, dp.norm, 1, dp.fac,
                                         b.dp_sums, 1, im.v_depth, im.v_alpha);
+    if (!rc && (bg.colors || at.target))   // im.v_rgb is d loss / d composite here, and d loss / d render as it stands
+        rc = st3r_alpha_grad_impl(ctx, s, ro.C, ro.H, ro.W, im.alpha, bg.colors, bg.colors ? im.v_rgb : nullptr, at.target,
+                                  at.weight, at.norm, 1, at.fac, dp.prior ? im.v_alpha : nullptr, b.at_sums, 1, im.v_alpha,
+                                  nullptr);
     st3r_prof_end(ctx, s, STG_LOSS);
     return rc;
 }
@@ -399,14 +429,20 @@ static int train_views(st3r_ctx* ctx, hipStream_t s, const GsParams& g, const Vi
     LossWeight lw{};
     if (b.weighted) rc = st3r_loss_weight_for(ctx, s, b.gt, v.C, v.H, v.W, &lw);
     if (rc) return rc;
+    Background bg{};
+    if (b.background) st3r_background_for(ctx, b.gt, v.C, v.H, v.W, &bg);
+    AlphaTarget at{};
+    if (b.at_sums) rc = st3r_alpha_target_for(ctx, s, b.gt, v.C, v.H, v.W, &at);
+    if (rc) return rc;
     // The one decision: with a depth prior the projection backward reads the per-pair array v_pairs (colour + depth
-    // gradients, added), without one it sums the colour backward's slots itself.
+    // gradients, added), without one it sums the colour backward's slots itself (backgrounds and alpha targets hand the
+    // colour backward a v_alpha as the depth prior does; its slots then carry the alpha path, and need_pairs stays false).
     const bool need_pairs = dp.prior != nullptr;
     RasterOut& ro = *ro_out;
     rc = rasterize_front(ctx, s, g, v, reg_sums, 1, nullptr, allow_async, &ro, b.sums);
     if (rc) return rc;
     StepImages im;
-    rc = step_images(ctx, ro, need_pairs, ex.exposure != nullptr, &im);
+    rc = step_images(ctx, ro, need_pairs, ex.exposure != nullptr, bg.colors != nullptr, bg.colors || at.target, &im);
     if (rc) return rc;
     // an intrinsics gradient registered for these views (st3r_ctx_set_intrinsics_grad): it needs the per-pair array as
     // the pose gradient does
@@ -416,7 +452,7 @@ static int train_views(st3r_ctx* ctx, hipStream_t s, const GsParams& g, const Vi
         ARENA_GET(SLOT_VSPLATS, float, ro.n_pairs * ST3R_SPLAT_STRIDE, vp);
         v_pairs = vp;
     }
-    rc = forward_and_losses(ctx, s, ro, b, f.ssim, true, dp, ex, lw, im);
+    rc = forward_and_losses(ctx, s, ro, b, f.ssim, true, dp, ex, lw, im, bg, at);
     if (rc) return rc;
     st3r_vtile_ref slots{};
     rc = blend_backward(ctx, s, ro, im, need_pairs, &slots, v_pairs);
@@ -524,6 +560,28 @@ int st3r_train_fwd_bwd_impl(st3r_ctx* ctx, hipStream_t s, const GsParams& g, con
                        "supported in view-sharded training (clear them with st3r_ctx_set_loss_weight(ctx, NULL, ...))");
         return ST3R_ERR_INVALID;
     }
+    // backgrounds registered for these views (st3r_ctx_set_background): the same rule
+    Background bg;
+    st3r_background_for(ctx, gt_images, C, v.H, v.W, &bg);
+    if (bg.colors && ctx->comm) {
+        st3r_set_error("backgrounds are registered and a communicator is attached -- backgrounds are not supported in "
+                       "view-sharded training (clear them with st3r_ctx_set_background(ctx, NULL, ...))");
+        return ST3R_ERR_INVALID;
+    }
+    // alpha targets registered for these views (st3r_ctx_set_alpha_target): their per-view sums, and the same rule
+    double* at_sums = nullptr;
+    AlphaTarget at;
+    rc = st3r_alpha_target_for(ctx, s, gt_images, C, v.H, v.W, &at);
+    if (rc) return rc;
+    if (at.target) {
+        if (ctx->comm) {
+            st3r_set_error("alpha targets are registered and a communicator is attached -- alpha supervision is not "
+                           "supported in view-sharded training (clear them with st3r_ctx_set_alpha_target(ctx, NULL, ...))");
+            return ST3R_ERR_INVALID;
+        }
+        ARENA_GET(SLOT_ATARGET_SUMS, double, (size_t)C, as);
+        at_sums = as;
+    }
     st3r_prof_next_step(ctx);
     rc = st3r_count_settle(ctx);
     if (rc) return rc;
@@ -532,13 +590,14 @@ int st3r_train_fwd_bwd_impl(st3r_ctx* ctx, hipStream_t s, const GsParams& g, con
     if ((ctx->debug_flags & 32) && chunks < 2) chunks = 2;
     if (chunks > C) chunks = C;
     int64_t stats[3];
-    rc = train_chunks(ctx, s, g, ViewBatch{v, gt_images, sums, dp_sums, v_viewmats, ex.exposure != nullptr, lw.weight != nullptr},
+    rc = train_chunks(ctx, s, g, ViewBatch{v, gt_images, sums, dp_sums, v_viewmats, ex.exposure != nullptr, lw.weight != nullptr,
+                                           bg.colors != nullptr, at_sums},
                       LossFacs{ssim_fac, opac_fac, scale_fac},
                       reg_sums, reg_sums + 4, stats_host != nullptr, grads, &chunks, stats);
     if (rc) return rc;
     if (chunks > 1) ctx->view_chunks = chunks;
     rc = finalize_loss(s, C, v.H, v.W, sums, reg_sums, ssim_fac, (double)C, (double)opac_fac / N,
-                       (double)scale_fac / (3.0 * N), loss_out, dp_sums, dp, lw);
+                       (double)scale_fac / (3.0 * N), loss_out, dp_sums, dp, lw, at_sums, at);
     if (rc) return rc;
     if (stats_host) {
         stats_host[0] = stats[0]; stats_host[1] = stats[1]; stats_host[2] = st3r_ctx_arena_bytes(ctx);
@@ -569,7 +628,7 @@ ST3R_EXPORT int st3r_gs_raster_train(st3r_ctx* ctx, void* stream, int N, int C, 
     hipStream_t s = (hipStream_t)stream;
     ARENA_GET(SLOT_SMALL, double, 2 * (size_t)C + 8, sums);
     double* reg_sums = sums + 2 * C;
-    const ViewBatch b{GsViews{C, width, height}, gt_images, sums, nullptr, nullptr, false, false};   // (no camera is looked at)
+    const ViewBatch b{GsViews{C, width, height}, gt_images, sums, nullptr, nullptr, false, false, false, nullptr};   // (no camera is looked at)
     HIP_TRY(hipMemsetAsync(reg_sums, 0, sizeof(double) * 4, s));  // stays zero: the regularisers belong to the owners
     st3r_prof_next_step(ctx);
     RasterOut ro;
@@ -579,7 +638,7 @@ ST3R_EXPORT int st3r_gs_raster_train(st3r_ctx* ctx, void* stream, int N, int C, 
     if (rc == ST3R_SPLIT_VIEWS) rc = ST3R_ERR_INVALID;
     if (rc) return rc;
     StepImages im;
-    rc = step_images(ctx, ro, false, false, &im);
+    rc = step_images(ctx, ro, false, false, false, false, &im);
     if (rc) return rc;
     rc = forward_and_losses(ctx, s, ro, b, ssim_fac, false, DepthPrior{}, ExposureReg{}, LossWeight{}, im);
     if (rc) return rc;

@@ -1,6 +1,6 @@
 // What the per-view kernels share: the fixed-order block sum of doubles (gs_pose_bwd.hip, gs_blend_depth.hip and the
-// two files below), the scaffold of the streaming per-view kernels (loss_depth.hip, gs_exposure.hip) with the weight
-// sums of both weighted losses (loss_depth.hip, loss.hip), a two-switch kernel launch, and the core of
+// two files below), the scaffold of the streaming per-view kernels (loss_depth.hip, gs_exposure.hip, gs_alpha.hip) with the
+// weight sums of the weighted losses (loss_depth.hip, loss.hip, gs_alpha.hip), a two-switch kernel launch, and the core of
 // the per-view Adam kernels (gs_pose_step.hip, gs_exposure.hip).  The device helpers are of the form DESIGN.md's "What
 // the projection kernels share" arrives at: references in the order of first use, no arrays by value.
 #pragma once

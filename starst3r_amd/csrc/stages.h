@@ -50,6 +50,12 @@ struct ExposureReg { const float* exposure; float* v_exposure; };
 // sums_stride: doubles per view of the loss kernel's accumulators
 struct LossWeight { const float* weight = nullptr; const double* norm = nullptr; int norm_stride = 0; int sums_stride = 2; };
 
+// the registered backgrounds [C,3] of a set of views (gs_alpha.hip); colors == NULL: none apply
+struct Background { const float* colors; };
+
+// the registered alpha targets of a set of views (gs_alpha.hip): target, weight [C,H,W], norm [C]; target == NULL: none apply
+struct AlphaTarget { const float* target; const float* weight; const double* norm; float fac; };
+
 // ---- api.hip, fused_step.hip, comm.hip ----
 // The 16 device words next to the fused steps: [0] record count of an asynchronous step (k_adam compares it with the
 // step's capacity), [4] status word of an exchanged step (comm.hip).  Zeroed when allocated.
@@ -133,6 +139,16 @@ void st3r_exposure_for(st3r_ctx* ctx, const float* gt, int C, int H, int W, Expo
 int st3r_exposure_fwd_impl(hipStream_t s, int C, int H, int W, const float* rgb, const float* exposure, float* out);
 int st3r_exposure_bwd_impl(st3r_ctx* ctx, hipStream_t s, int C, int H, int W, const float* rgb, const float* exposure,
                            const float* v_out, float* v_rgb, float* v_exposure);
+
+// ---- gs_alpha.hip ----
+void st3r_background_for(st3r_ctx* ctx, const float* gt, int C, int H, int W, Background* out);
+int st3r_alpha_target_for(st3r_ctx* ctx, hipStream_t s, const float* gt, int C, int H, int W, AlphaTarget* out);
+int st3r_composite_fwd_impl(hipStream_t s, int C, int H, int W, const float* rgb, const float* alpha,
+                            const float* backgrounds, float* out);
+int st3r_alpha_grad_impl(st3r_ctx* ctx, hipStream_t s, int C, int H, int W, const float* alpha, const float* backgrounds,
+                         const float* v_out, const float* target, const float* weight, const double* norm, int norm_stride,
+                         float alpha_fac, const float* v_alpha_in, double* sums, int sums_stride, float* v_alpha,
+                         float* v_backgrounds);
 
 // ---- gs_intrinsics.hip ----
 // the rows of the registered intrinsics gradient [C,4] of the C views at `gt`; NULL: none applies

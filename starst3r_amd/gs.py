@@ -272,6 +272,44 @@ class _Exposure(torch.autograd.Function):
         return v_rgb, v_exposure, None
 
 
+class _Composite(torch.autograd.Function):
+    """y = x + (1 - alpha) b per view (st3r_composite_fwd / st3r_alpha_grad): differentiable into the render, its alpha
+    and the backgrounds."""
+
+    @staticmethod
+    def forward(fctx, rgb, alpha, backgrounds, ctx):
+        rgb, alpha, backgrounds = rgb.contiguous(), alpha.contiguous(), backgrounds.contiguous()
+        fctx.save_for_backward(alpha, backgrounds)
+        fctx.ctx = ctx
+        return ops.composite_fwd(ctx, rgb, alpha, backgrounds)
+
+    @staticmethod
+    def backward(fctx, v_out):
+        alpha, backgrounds = fctx.saved_tensors
+        v_out = v_out.contiguous().float()
+        v_alpha, _, v_b = ops.alpha_grad(fctx.ctx, alpha, backgrounds, v_out, want_v_backgrounds=fctx.needs_input_grad[2])
+        return v_out, v_alpha, v_b, None
+
+
+def _render_backgrounds(scene, n_views, render_mode):
+    """scene.render_backgrounds as the (n_views, 3) tensor of this render, or None; its checks, before anything runs"""
+    B = getattr(scene, "render_backgrounds", None)
+    if B is None or B is False:
+        return None
+    if render_mode in ("D", "ED"):
+        raise ValueError(f"scene.render_backgrounds applies to the RGB channels: render_mode {render_mode!r} has none")
+    if B is True:
+        B = getattr(scene, "backgrounds", None)
+        if B is None:
+            raise ValueError("scene.render_backgrounds = True needs scene.backgrounds, one colour per image: there are none")
+        B = torch.as_tensor(np.asarray(B) if not torch.is_tensor(B) else B, dtype=torch.float32)
+    if not torch.is_tensor(B) or tuple(B.shape) != (n_views, 3):
+        shape = tuple(B.shape) if torch.is_tensor(B) else type(B).__name__
+        raise ValueError(f"scene.render_backgrounds must be None, True or a tensor of shape ({n_views}, 3), one colour per "
+                         f"rendered view, got {shape}")
+    return B
+
+
 def _check_render_exposure(exposure, n_views, render_mode):
     """the checks of render_3dgs(exposure=...), before anything runs"""
     if render_mode in ("D", "ED"):
@@ -291,12 +329,20 @@ def render_3dgs(scene, w2c: torch.Tensor, intrinsics: torch.Tensor, width: int, 
     with the depth last.  Every mode back-propagates into the Gaussians and, when it requires a gradient, into w2c.
     exposure (not in the reference): a (N,3,4) tensor, one affine colour transform [A | t] per view, applied to the RGB
     channels of render_img (y = A x + t); differentiable into the Gaussians, w2c and exposure.
+    scene.render_backgrounds (gsplat.rasterization's `backgrounds`, which the reference does not pass on; a setting of the
+    scene like intrinsics_grad, for the same reason; absent or None: off): a (N,3) tensor, one colour per rendered view,
+    under the RGB channels of render_img (y = x + (1 - alpha) b), before exposure -- scene first, then camera; True stands
+    for scene.backgrounds, the colours run_3dgs_optim trains against (N = len(scene.imgs), as in render_3dgs_original;
+    ValueError when there are none).  The depth channel of "RGB+D" / "RGB+ED" gets no background (gsplat pads it with 0),
+    "D" / "ED" raise ValueError as they do for exposure; differentiable into the Gaussians (through the colours and through
+    alpha), w2c, the intrinsics (under scene.intrinsics_grad) and the tensor itself.
     scene.intrinsics_grad (not in the reference; gsplat returns no such gradient; a setting of the scene, default False,
     because the argument list above is the boundary users program against): True makes the backward pass return
     d loss / d intrinsics as well when `intrinsics` requires a gradient -- (N,3,3), non-zero at fx, fy, cx, cy -- in every
     render_mode; with False no kernel for it runs and intrinsics.grad stays None."""
     if render_mode not in RENDER_MODES:
         raise ValueError(f"render_mode must be one of {RENDER_MODES}, got {render_mode!r}")
+    backgrounds = _render_backgrounds(scene, w2c.shape[0], render_mode)
     if exposure is not None:
         _check_render_exposure(exposure, w2c.shape[0], render_mode)
     g = scene.gaussians
@@ -304,15 +350,21 @@ def render_3dgs(scene, w2c: torch.Tensor, intrinsics: torch.Tensor, width: int, 
     w2c = w2c.to(scene.device, torch.float32).contiguous(); Ks = intrinsics.to(scene.device, torch.float32).contiguous()
     if exposure is not None:
         exposure = exposure.to(scene.device, torch.float32)
+    if backgrounds is not None:
+        backgrounds = backgrounds.to(scene.device, torch.float32)
     out = _Rasterize.apply(g["means"], g["quats"], g["scales"], g["opacities"], g["shN"], w2c, Ks, width, height, ctx,
                            render_mode != "RGB", bool(getattr(scene, "intrinsics_grad", False)))
     if render_mode == "RGB":
         rgb, alpha = out
+        if backgrounds is not None:
+            rgb = _Composite.apply(rgb, alpha, backgrounds, ctx)
         img = rgb if exposure is None else _Exposure.apply(rgb, exposure, ctx)
     else:
         rgb, alpha, depth = out
         if render_mode.endswith("ED"):
             depth = depth / alpha.clamp(min=1e-10)
+        if backgrounds is not None and render_mode.startswith("RGB"):
+            rgb = _Composite.apply(rgb, alpha, backgrounds, ctx)
         if exposure is not None and render_mode.startswith("RGB"):
             rgb = _Exposure.apply(rgb, exposure, ctx)
         img = torch.cat([rgb, depth], dim=-1) if render_mode.startswith("RGB") else depth
@@ -323,7 +375,8 @@ def render_3dgs(scene, w2c: torch.Tensor, intrinsics: torch.Tensor, width: int, 
 
 def render_3dgs_original(scene, width: int, height: int, render_mode: str = "RGB", exposure=False):
     """Render from camera views of original scene (reference gs.py:90-95).  exposure=True (not in the reference): through
-    the trained scene.exposures (run_3dgs_optim(exposure_lr=...)), i.e. as the photographs were taken."""
+    the trained scene.exposures (run_3dgs_optim(exposure_lr=...)), i.e. as the photographs were taken.  With
+    scene.render_backgrounds = True the render lies over scene.backgrounds (see render_3dgs)."""
     if exposure:
         E = getattr(scene, "exposures", None)
         if E is None:
@@ -657,6 +710,133 @@ class _LossMasks(_PerViewOption):
         ops.set_loss_weight(c.ctx, None, None)
 
 
+def _as_tensor(a):
+    """a tensor or whatever numpy makes an array of, as a (detached) tensor"""
+    return a.detach() if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))
+
+
+class _Backgrounds(_PerViewOption):
+    """scene.backgrounds: one fixed colour per image under its render, registered with the ctx for the fused step's composite"""
+    spelled, schedule = "scene.backgrounds", False
+
+    @classmethod
+    def when_on(cls, scene, enable_pruning, backgrounds):
+        """switched on by the colours themselves: off when absent or None"""
+        if backgrounds is None:
+            return None
+        try:
+            b = _as_tensor(backgrounds)
+        except Exception:
+            b = None
+        n = len(scene.imgs)
+        if b is None or b.dtype == torch.bool or b.is_complex() or tuple(b.shape) != (n, 3):
+            shape = type(backgrounds).__name__ if b is None else f"{b.dtype} {tuple(b.shape)}"
+            raise ValueError(f"scene.backgrounds is one colour per image, a numeric array or tensor of shape ({n}, 3), got {shape}")
+        if not bool(torch.isfinite(b.double()).all()):
+            raise ValueError("scene.backgrounds holds non-finite entries")
+        _single_replica_only(cls.spelled, scene, enable_pruning)
+        return cls(scene, backgrounds, b)
+
+    def __init__(self, scene, backgrounds, as_tensor):
+        self.given, self.tensor = backgrounds, as_tensor
+
+    def set_up(self, c):   # uploaded once and cached like the loss masks (identity and version of what the scene holds)
+        key = (id(self.given), getattr(self.given, "_version", None), tuple(c.views))
+        cached = getattr(c.scene, "_backgrounds_dev", None)
+        if cached is None or cached[0] != key:
+            colors = self.tensor.to(c.scene.device, torch.float32)[list(c.views)].contiguous()
+            c.scene._backgrounds_dev = (key, colors, self.given)   # (the object is kept: its id stays its own)
+        self.colors = c.scene._backgrounds_dev[1]
+
+    def register(self, c):
+        ops.set_background(c.ctx, c.gt, self.colors)
+
+    def clear(self, c):
+        ops.set_background(c.ctx, None, None)
+
+
+def _alpha_maps_key(masks, weights, height, width):
+    """what the cached upload of scene.alpha_masks / alpha_weights is keyed by (as _loss_masks_key)"""
+    return (_loss_masks_key(masks, height, width), None if weights is None else _loss_masks_key(weights, height, width))
+
+
+def _check_alpha_maps(scene, name, maps, height, width, upper):
+    """ValueError unless scene.<name> is one entry per image, each None or an [H,W] map, bool or numeric, of finite values
+    in [0, upper] (upper None: >= 0)"""
+    if isinstance(maps, (np.ndarray, torch.Tensor)) or not hasattr(maps, "__len__"):
+        raise ValueError(f"scene.{name} is a list with one entry per image (None or an [H,W] map), got {type(maps).__name__}")
+    if len(maps) != len(scene.imgs):
+        raise ValueError(f"scene.{name} holds {len(maps)} entries for {len(scene.imgs)} images")
+    for i, m in enumerate(maps):
+        if m is not None and tuple(getattr(m, "shape", ())) != (height, width):
+            raise ValueError(f"scene.{name}[{i}] has shape {tuple(getattr(m, 'shape', ()))}, its image ({height}, {width})")
+    for i, m in enumerate(maps):
+        if m is None:
+            continue
+        t = _as_tensor(m)
+        if t.dtype == torch.bool:
+            continue
+        bad = t.is_complex() or not bool(torch.isfinite(t).all()) or bool((t < 0).any()) or \
+            (upper is not None and bool((t > upper).any()))
+        if bad:
+            allowed = "finite and >= 0" if upper is None else f"finite and in [0, {upper}]"
+            raise ValueError(f"scene.{name}[{i}] holds entries out of range: the values are {allowed}")
+
+
+class _AlphaMasks(_PerViewOption):
+    """scene.alpha_fac with scene.alpha_masks / scene.alpha_weights: per-view targets of the render's accumulated opacity,
+    registered with the ctx for the fused step's alpha term"""
+    spelled, schedule = "scene.alpha_fac", False
+
+    @classmethod
+    def when_on(cls, scene, enable_pruning, alpha_fac, masks, weights):
+        """the maps are checked whenever they are there; off when alpha_fac == 0 or every mask is None"""
+        if isinstance(alpha_fac, bool) or not isinstance(alpha_fac, (int, float, np.floating, np.integer)) or \
+                not np.isfinite(float(alpha_fac)):
+            raise ValueError(f"scene.alpha_fac is a plain finite float, got {alpha_fac!r}")
+        height, width = scene.imgs[0].shape[:2]
+        cached = getattr(scene, "_alpha_maps_dev", None)
+        scanned = cached is not None and masks is not None and cached[0] == _alpha_maps_key(masks, weights, height, width)
+        if masks is not None and not scanned:   # (the values of maps that are already uploaded are not scanned again)
+            _check_alpha_maps(scene, "alpha_masks", masks, height, width, 1)
+        if weights is not None and not scanned:
+            _check_alpha_maps(scene, "alpha_weights", weights, height, width, None)
+        if float(alpha_fac) == 0.0:
+            return None
+        if masks is None:
+            raise ValueError("scene.alpha_fac != 0 needs one target per image in scene.alpha_masks: there are none")
+        if all(m is None for m in masks):
+            return None
+        _single_replica_only(cls.spelled, scene, enable_pruning)
+        return cls(scene, float(alpha_fac), masks, weights)
+
+    def __init__(self, scene, alpha_fac, masks, weights):
+        self.fac, self.masks, self.weight_maps = alpha_fac, masks, weights
+
+    def set_up(self, c):   # uploaded once and cached like the loss masks
+        scene, H, W = c.scene, c.height, c.width
+        key = _alpha_maps_key(self.masks, self.weight_maps, H, W)
+        cached = getattr(scene, "_alpha_maps_dev", None)
+        if cached is None or cached[0] != key or cached[1] != tuple(c.views):
+            def on_device(m, fill):
+                if m is None:
+                    return torch.full((H, W), fill, dtype=torch.float32, device=scene.device)
+                return _as_tensor(m).to(scene.device, torch.float32)
+            target = torch.stack([on_device(self.masks[i], 0.0) for i in c.views]).contiguous()
+            # a view without a target is not supervised: weight 0 whatever alpha_weights holds for it
+            weight = torch.stack([on_device(None if self.masks[i] is None or self.weight_maps is None else self.weight_maps[i],
+                                            0.0 if self.masks[i] is None else 1.0) for i in c.views]).contiguous()
+            scene._alpha_maps_dev = (key, tuple(c.views), target, weight, list(self.masks),
+                                     None if self.weight_maps is None else list(self.weight_maps))
+        self.target, self.weights = scene._alpha_maps_dev[2], scene._alpha_maps_dev[3]
+
+    def register(self, c):
+        ops.set_alpha_target(c.ctx, c.gt, self.target, self.weights, self.fac)
+
+    def clear(self, c):
+        ops.set_alpha_target(c.ctx, None, None, None)
+
+
 def _iterations(iters, verbose):
     """range(iters), with a progress bar when verbose"""
     if verbose:
@@ -760,14 +940,38 @@ def run_3dgs_optim(
     the entries' identities and versions: assign a new array instead of editing one in place).  Works together with
     pose_lr, depth_fac, exposure_lr, scene.intrinsics_lr and enable_pruning; single process, Gaussians replicated only.
     With loss_masks absent, None, or every entry None nothing about the call changes and nothing is registered.
+
+    scene.backgrounds (not in the reference, which renders on black; a setting of the scene like loss_masks, default absent
+    or None): an array or tensor [len(scene.imgs),3], finite -- the colour under every view's render inside the same fused
+    step, y = x + (1 - alpha) b before the exposure (scene first, then camera): photographs of an object on a white backdrop,
+    or a masked-out object composited on white, can then be trained against without Gaussians that paint the backdrop.  The
+    colours are fixed, not trained; with scene.render_backgrounds = True the render calls lay them under their image.
+
+    scene.alpha_fac, scene.alpha_masks, scene.alpha_weights (not in the reference; settings of the scene, defaults 0.0, absent,
+    absent).  alpha_fac is a plain float: when not 0.0 the loss of every view gains a silhouette term inside the same fused
+    step, alpha_fac * sum_p w |alpha - M| / max(sum_p w, 1), alpha the accumulated opacity of the render.  alpha_masks is a
+    list with one entry per image, each None (that view is not supervised: weight 0) or an [H,W] map M in [0,1], bool or
+    numeric; alpha_weights, optional, has the same layout: None entries are all ones, values are finite and >= 0, and a 0
+    marks the "don't know" pixels of a trimap.  Together with loss_masks this lets an object mask do its job in the dropped
+    pixels: the photometric loss ignores them, the alpha term pushes alpha to 0 outside the mask and to 1 inside it.
+    alpha_fac != 0 without alpha_masks raises ValueError, as depth_fac does without depth maps; with alpha_fac == 0, or every
+    mask None, the option is off.  The returned losses include the alpha term.
+
+    For both: wrong count, wrong shape, values out of range or non-finite raise ValueError before anything runs; the uploads
+    are cached and keyed like the loss masks'; they work together with pose_lr, depth_fac, exposure_lr, scene.intrinsics_lr,
+    scene.loss_masks and enable_pruning; single process, Gaussians replicated only.  With both off nothing about the call
+    changes and nothing is registered.
     """
     masks = _LossMasks.when_on(scene, enable_pruning, getattr(scene, "loss_masks", None))   # (its checks come first)
+    backgrounds = _Backgrounds.when_on(scene, enable_pruning, getattr(scene, "backgrounds", None))
+    alphas = _AlphaMasks.when_on(scene, enable_pruning, getattr(scene, "alpha_fac", 0.0), getattr(scene, "alpha_masks", None),
+                                 getattr(scene, "alpha_weights", None))
     depth = _DepthPrior.when_on(scene, enable_pruning, depth_fac, depth_conf_thres)
     poses = _Poses.when_on(scene, enable_pruning, pose_lr, pose_freeze)
     exposures = _Exposures.when_on(scene, enable_pruning, exposure_lr, exposure_freeze)
     intrinsics = _Intrinsics.when_on(scene, enable_pruning, getattr(scene, "intrinsics_lr", 0.0))
     # in this order at every hook: checks (above), set-up, registration, clearing, behind the step, finish
-    options = [o for o in (depth, poses, exposures, intrinsics, masks) if o is not None]
+    options = [o for o in (depth, poses, exposures, intrinsics, masks, backgrounds, alphas) if o is not None]
     counters = [o.counter for o in options if o.counter]
     height, width = scene.imgs[0].shape[:2]
     ctx = ops.get_context(scene.device)

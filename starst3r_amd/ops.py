@@ -408,6 +408,73 @@ def set_exposure(ctx, gt, exposure, v_exposure):
                       lambda: tuple(exposure.shape) == (gt.shape[0], 3, 4) and v_exposure.shape == exposure.shape)
 
 
+def _alpha_shapes(alpha, backgrounds=None, **images):
+    """(C, H, W) of alpha [C,H,W,1]; ValueError unless backgrounds is [C,3], every named image [C,H,W,3] or, for a name
+    ending in `map`, [C,H,W] -- float32 all of them (None entries are skipped)"""
+    if alpha.dim() != 4 or alpha.shape[-1] != 1 or alpha.dtype != torch.float32:
+        raise ValueError(f"expected float32 alpha [C,H,W,1], got {alpha.dtype} {tuple(alpha.shape)}")
+    Cn, H, W = alpha.shape[:3]
+    if backgrounds is not None and (tuple(backgrounds.shape) != (Cn, 3) or backgrounds.dtype != torch.float32):
+        raise ValueError(f"expected float32 backgrounds ({Cn}, 3), got {backgrounds.dtype} {tuple(backgrounds.shape)}")
+    for name, t in images.items():
+        want = (Cn, H, W) if name.endswith("map") else ((Cn, H, W, 1) if name.startswith("v_alpha") else (Cn, H, W, 3))
+        if t is not None and (tuple(t.shape) != want or t.dtype != torch.float32):
+            raise ValueError(f"expected float32 {name} {want}, got {t.dtype} {tuple(t.shape)}")
+    return Cn, H, W
+
+
+def composite_fwd(ctx, rgb, alpha, backgrounds, out=None):
+    """The render rgb [C,H,W,3] with accumulated opacity alpha [C,H,W,1] over the views' background colours [C,3]:
+    y = x + (1 - alpha) b per pixel (st3r_composite_fwd).  out may be rgb itself (in place)."""
+    Cn, H, W = _alpha_shapes(alpha, backgrounds, rgb=rgb, out=out)
+    out = torch.empty_like(rgb) if out is None else out
+    _lib.check(_lib.lib().st3r_composite_fwd(ctx.handle, _stream(), Cn, H, W, _p(rgb), _p(alpha), _p(backgrounds), _p(out)))
+    return out
+
+
+def alpha_grad(ctx, alpha, backgrounds=None, v_out=None, target=None, weight=None, alpha_fac=0.0, v_alpha_in=None,
+               v_alpha=None, want_v_backgrounds=False):
+    """d loss / d alpha of a render [C,H,W,1] besides the depth prior's, in one pass (st3r_alpha_grad).  Background term
+    (backgrounds [C,3] and v_out = d loss / d composite [C,H,W,3]): -sum_j b_j v_j, and with want_v_backgrounds
+    v_backgrounds [C,3] = sum_p (1 - alpha) v.  Alpha term (target, weight [C,H,W], alpha_fac): the derivative of
+    alpha_fac * sum_p w |alpha - target| / max(sum_p w, 1) per view.  v_alpha_in: added first; v_alpha (output) may be
+    v_alpha_in itself.  Returns (v_alpha, sums [C,2] float64 -- sum_p w |alpha - target| and n_c -- or None,
+    v_backgrounds or None)."""
+    Cn, H, W = _alpha_shapes(alpha, backgrounds, v_out=v_out, target_map=target, weight_map=weight, v_alpha_in=v_alpha_in,
+                             v_alpha=v_alpha)
+    if (backgrounds is None) != (v_out is None) or (target is None) != (weight is None):
+        raise ValueError("a term is given whole: backgrounds with v_out, target with weight")
+    if backgrounds is None and target is None:
+        raise ValueError("alpha_grad needs the background term, the alpha term or both")
+    v_alpha = torch.empty_like(alpha) if v_alpha is None else v_alpha
+    sums = torch.empty((Cn, 2), dtype=torch.float64, device=alpha.device) if target is not None else None
+    v_b = torch.empty((Cn, 3), dtype=torch.float32, device=alpha.device) if want_v_backgrounds and backgrounds is not None \
+        else None
+    _lib.check(_lib.lib().st3r_alpha_grad(ctx.handle, _stream(), Cn, H, W, _p(alpha), _p(backgrounds), _p(v_out), _p(target),
+                                          _p(weight), float(alpha_fac), _p(v_alpha_in), _p(sums, torch.float64), _p(v_alpha),
+                                          _p(v_b)))
+    return v_alpha, sums, v_b
+
+
+def set_background(ctx, gt, backgrounds):
+    """Register the background colours [C,3] (float32) of the images gt [C,H,W,3] with the ctx -- train_fwd_bwd, train_step
+    and train_step_poses on `gt` (or whole views of it) then compare the render composited over them with the ground truth
+    (st3r_ctx_set_background) -- or clear the registration (gt = None).  The caller's tensors are kept alive here."""
+    _set_registration(ctx, "background", "_bg_keep", gt, (backgrounds,),
+                      lambda: backgrounds.is_contiguous() and backgrounds.dtype == torch.float32 and
+                      tuple(backgrounds.shape) == (gt.shape[0], 3))
+
+
+def set_alpha_target(ctx, gt, target, weight, alpha_fac=1.0):
+    """Register alpha targets (target, weight [C,H,W] float32) for the images gt [C,H,W,3] with the ctx -- train_fwd_bwd,
+    train_step and train_step_poses on `gt` (or whole views of it) then add alpha_fac * sum_p w |alpha - target| /
+    max(sum_p w, 1) per view to their loss (st3r_ctx_set_alpha_target) -- or clear the registration (gt = None).  The
+    caller's tensors are kept alive here and must stay unchanged while registered."""
+    _set_registration(ctx, "alpha_target", "_at_keep", gt, (target, weight),
+                      lambda: all(t.is_contiguous() and t.dtype == torch.float32 and t.shape == tuple(gt.shape[:3])
+                                  for t in (target, weight)), float(alpha_fac))
+
+
 def intrinsics_adam_step(ctx, Ks, v_Ks, k_m, k_v, lr, b1, b2, eps, step, mask, W, H, tie_focal=True, opt_pp=False):
     """One Adam step on the intrinsics Ks [C,3,3], in place, from v_Ks [C,4] = d loss / d (fx, fy, cx, cy); moments
     k_m / k_v [4C]; the parameters are (log fx, log fy, cx / W, cy / H) (st3r_intrinsics_adam_step).  tie_focal: one
