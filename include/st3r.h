@@ -371,6 +371,41 @@ int st3r_ctx_set_background(st3r_ctx* ctx, const float* gt, const float* backgro
 int st3r_ctx_set_alpha_target(st3r_ctx* ctx, const float* gt, const float* target, const float* weight, int C, int height,
                               int width, float alpha_fac);
 
+/* ---- Activated scales and opacities: the canonical 3DGS parameterisation (csrc/gs_activation.hip) ----
+ * The reference renders its scales and opacities raw while its regularisers and the MCMC refinement read the same tensors
+ * as logs and logits; that stays the default.  With the activation the tensors ARE log-scales and logits:
+ *   S = expf(s) over the 3N floats, O = 1 / (1 + expf(-o)) over the N floats        float32, precise expf
+ * st3r_param_activate writes both; reg_sums (device, double[2], or NULL) receives sum O and sum S -- the sums of the
+ * STORED float32 values, in double, block partials finished in a fixed order, no atomics: the same inputs give the same
+ * bits.  A logit of -90 gives exactly 0, one of +90 exactly 1.
+ * st3r_param_activate_bwd is the chain rule on the stored activated values, without a transcendental:
+ *   v_s = (v_S + reg_s_k) * S                  v_o = ((v_O + reg_o_k) * O) * (1 - O)        float32, in that order
+ * reg_s_k / reg_o_k carry the gradient of regularisers k sum S / k sum O (0: the plain chain rule).  v_scales may be
+ * v_act_scales and v_opacities may be v_act_opacities (in place).  Both take 16-byte accesses when every pointer lies on a
+ * 16-byte boundary (the up to three Gaussians behind the last multiple of four go one by one) and 4-byte accesses
+ * otherwise; the results do not depend on the form. */
+int st3r_param_activate(st3r_ctx* ctx, void* stream, int N, const float* scales, const float* opacities,
+                        float* act_scales, float* act_opacities, double* reg_sums);
+int st3r_param_activate_bwd(st3r_ctx* ctx, void* stream, int N, const float* act_scales, const float* act_opacities,
+                            const float* v_act_scales, const float* v_act_opacities, float reg_s_k, float reg_o_k,
+                            float* v_scales, float* v_opacities);
+
+/* The activation as a setting of the context (on = 0 / 1; a context starts with 0), like the exchange form.  While on,
+ * st3r_gs_train_fwd_bwd / _step / _step_poses and st3r_gs_render read `scales` as log-scales and `opacities` as logits:
+ * st3r_param_activate into scratch of the context (with the two sums), the whole step of the raw path on the activated
+ * copies with opac_fac = scale_fac = 0 -- projection, blend, losses, every registration, pose and intrinsics gradients see
+ * activated geometry, kernel for kernel --, then ONE st3r_param_activate_bwd in place on the scales and opacities blocks
+ * of `grads`, behind the last view chunk, with reg_s_k = C * scale_fac / (3 N) and reg_o_k = C * opac_fac / N (float32, as
+ * the projection backward forms them).  The loss adds C * (opac_fac * sum O / N + scale_fac * sum S / (3 N)): the
+ * reference's regularisers, now functions of what is rendered.  Adam updates the caller's logs and logits.  The fused
+ * gradients and parameters are those of the chain st3r_param_activate -> training call on the copies with both factors 0
+ * -> st3r_param_activate_bwd -> st3r_adam_step, bit for bit.  The overflow protocol is unchanged: the copies are rebuilt
+ * from the parameters by every call.  With the setting off every call runs exactly the launches it ran before.  With a
+ * communicator attached the training calls return ST3R_ERR_INVALID while it is on; st3r_gs_raster_train takes records and
+ * is not concerned. */
+int st3r_ctx_set_activation(st3r_ctx* ctx, int on);
+int st3r_ctx_get_activation(st3r_ctx* ctx, int* on);
+
 /* Gradient of the render loss with respect to each camera's intrinsics, from the per-pair gradients v_splats of
  * st3r_gs_blend_bwd (floats 0-1 and 3-5; colour and depth do not depend on K): v_Ks [C,4] = d loss / d (fx, fy, cx, cy),
  * written whole.  Per visible pair (radius > 0), in float32, with p = R m + t = (x, y, z), the projection Jacobian

@@ -58,6 +58,10 @@ SIGNATURES = {
     "st3r_alpha_grad": [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, f32, vp, vp, vp, vp],
     "st3r_ctx_set_background": [vp, vp, vp, i32, i32, i32],
     "st3r_ctx_set_alpha_target": [vp, vp, vp, vp, i32, i32, i32, f32],
+    "st3r_param_activate": [vp, vp, i32, vp, vp, vp, vp, vp],
+    "st3r_param_activate_bwd": [vp, vp, i32, vp, vp, vp, vp, f32, f32, vp, vp],
+    "st3r_ctx_set_activation": [vp, i32],
+    "st3r_ctx_get_activation": [vp, C.POINTER(i32)],
     "st3r_gs_intrinsics_bwd": [vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, i32, f32, vp, vp, vp],
     "st3r_intrinsics_adam_step": [vp, vp, i32, vp, vp, vp, vp, f64, f64, f64, f64, i32, vp, i32, i32, i32],
     "st3r_ctx_set_intrinsics_grad": [vp, vp, vp, i32, i32, i32],

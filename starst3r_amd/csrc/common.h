@@ -97,6 +97,9 @@ enum ArenaSlot {
     SLOT_ATARGET_PART, // alpha targets (gs_alpha.hip): one double partial per (view, workgroup) of the weights' sums
     SLOT_ATARGET_NORM, // the same: n_c = max(sum w_c, 1) of every registered view, computed once per registration
     SLOT_ATARGET_SUMS, // the same: sum_p w |a - M| per view of the fused step
+    SLOT_ACT_SCALES,  // activated parameters (gs_activation.hip): exp(scales) [N,3] of the fused step / st3r_gs_render
+    SLOT_ACT_OPACITIES, // the same: sigmoid(opacities) [N]
+    SLOT_ACT_PART,    // the same: one 2-double partial per workgroup of (sum sigmoid, sum exp)
     SLOT_COUNT
 };
 
@@ -180,6 +183,9 @@ struct st3r_ctx {
     // alpha targets (st3r_ctx_set_alpha_target, gs_alpha.hip); at_fac == 0: none; at_norm_valid: SLOT_ATARGET_NORM holds
     // the n_c of this registration (computed by the first training call that uses it)
     ViewReg at; const float* at_target; const float* at_weight; float at_fac; int at_norm_valid;
+    // activated parameters (st3r_ctx_set_activation, gs_activation.hip): the fused steps and st3r_gs_render read the scales
+    // as logs and the opacities as logits
+    int activation;
     int bwd_stamp;  // generation stamp of the per-(record, tile) partial-gradient slots
     int depth_stamp;  // the same for the depth backward's slots (SLOT_VTILE_DEPTH)
     uint32_t scan_gen;   // single-pass scan (gs_isect.hip): generation of its status words

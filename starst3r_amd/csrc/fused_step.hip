@@ -582,21 +582,48 @@ int st3r_train_fwd_bwd_impl(st3r_ctx* ctx, hipStream_t s, const GsParams& g, con
         ARENA_GET(SLOT_ATARGET_SUMS, double, (size_t)C, as);
         at_sums = as;
     }
+    // activated parameters (st3r_ctx_set_activation): the same rule
+    const bool activated = ctx->activation != 0;
+    if (activated && ctx->comm) {
+        st3r_set_error("the activation is on and a communicator is attached -- activated scales and opacities are not "
+                       "supported in view-sharded training (clear it with st3r_ctx_set_activation(ctx, 0))");
+        return ST3R_ERR_INVALID;
+    }
     st3r_prof_next_step(ctx);
     rc = st3r_count_settle(ctx);
     if (rc) return rc;
+    // Activated: the step below runs on exp(scales) and sigmoid(opacities), copies in scratch rebuilt by every call, with
+    // both regulariser factors 0 -- every kernel sees activated geometry, unchanged.  The sums the projection still
+    // leaves in reg_sums[0..1] are then of the wrong tensors and are not used: the activation's own two, next to
+    // reg_sums, take their place in the loss.
+    GsParams ga = g;
+    double* const act_sums = small + 2 * C + 8;   // [2]: sum sigmoid(o), sum exp(s)
+    if (activated) {
+        rc = st3r_activated_params(ctx, s, g, act_sums, &ga);
+        if (rc) return rc;
+    }
     // the chunk count sticks to the context; debug flag 32 starts at two chunks (tests)
     int chunks = ctx->view_chunks > 0 ? ctx->view_chunks : 1;
     if ((ctx->debug_flags & 32) && chunks < 2) chunks = 2;
     if (chunks > C) chunks = C;
     int64_t stats[3];
-    rc = train_chunks(ctx, s, g, ViewBatch{v, gt_images, sums, dp_sums, v_viewmats, ex.exposure != nullptr, lw.weight != nullptr,
-                                           bg.colors != nullptr, at_sums},
-                      LossFacs{ssim_fac, opac_fac, scale_fac},
+    rc = train_chunks(ctx, s, ga, ViewBatch{v, gt_images, sums, dp_sums, v_viewmats, ex.exposure != nullptr, lw.weight != nullptr,
+                                            bg.colors != nullptr, at_sums},
+                      activated ? LossFacs{ssim_fac, 0.f, 0.f} : LossFacs{ssim_fac, opac_fac, scale_fac},
                       reg_sums, reg_sums + 4, stats_host != nullptr, grads, &chunks, stats);
     if (rc) return rc;
     if (chunks > 1) ctx->view_chunks = chunks;
-    rc = finalize_loss(s, C, v.H, v.W, sums, reg_sums, ssim_fac, (double)C, (double)opac_fac / N,
+    if (activated) {
+        // the chain rule, once, behind the last view chunk, in place on the scales and opacities blocks of grads (block
+        // layout: means 3N, quats 4N, scales 3N, opacities N, sh); the regularisers' gradient rides along, its constants
+        // formed as the projection backward forms them
+        const float reg_o_k = (float)C * opac_fac / (float)N, reg_s_k = (float)C * scale_fac / (3.0f * (float)N);
+        float* const v_s = grads + 7 * (size_t)N;
+        float* const v_o = grads + 10 * (size_t)N;
+        rc = st3r_param_activate_bwd_impl(s, N, ga.scales, ga.opacities, v_s, v_o, reg_s_k, reg_o_k, v_s, v_o);
+        if (rc) return rc;
+    }
+    rc = finalize_loss(s, C, v.H, v.W, sums, activated ? act_sums : reg_sums, ssim_fac, (double)C, (double)opac_fac / N,
                        (double)scale_fac / (3.0 * N), loss_out, dp_sums, dp, lw, at_sums, at);
     if (rc) return rc;
     if (stats_host) {
@@ -667,7 +694,12 @@ ST3R_EXPORT int st3r_gs_render(st3r_ctx* ctx, void* stream, int N, int C, const 
     RasterOut ro;
     int rc = st3r_count_settle(ctx);
     if (rc) return rc;
-    rc = rasterize_front(ctx, s, GsParams{N, means, quats, scales, opacities, sh, sh_stride},
+    GsParams g{N, means, quats, scales, opacities, sh, sh_stride};
+    if (ctx->activation) {   // log-scales and logits (st3r_ctx_set_activation): render their activated copies
+        rc = st3r_activated_params(ctx, s, g, nullptr, &g);
+        if (rc) return rc;
+    }
+    rc = rasterize_front(ctx, s, g,
                          GsViews{C, width, height, viewmats, Ks, campos}, nullptr, 0, nullptr, false, &ro);
     if (rc == ST3R_SPLIT_VIEWS) rc = ST3R_ERR_INVALID;
     if (rc) return rc;

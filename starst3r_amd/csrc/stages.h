@@ -150,6 +150,17 @@ int st3r_alpha_grad_impl(st3r_ctx* ctx, hipStream_t s, int C, int H, int W, cons
                          float alpha_fac, const float* v_alpha_in, double* sums, int sums_stride, float* v_alpha,
                          float* v_backgrounds);
 
+// ---- gs_activation.hip ----
+// S = exp(scales), O = sigmoid(opacities); reg_sums != NULL: double[2] = sum O, sum S of the stored values
+int st3r_param_activate_impl(st3r_ctx* ctx, hipStream_t s, int N, const float* scales, const float* opacities,
+                             float* act_scales, float* act_opacities, double* reg_sums);
+// v_s = (v_S + reg_s_k) S, v_o = (v_O + reg_o_k) O (1 - O); the outputs may be v_act_scales / v_act_opacities
+int st3r_param_activate_bwd_impl(hipStream_t s, int N, const float* act_scales, const float* act_opacities,
+                                 const float* v_act_scales, const float* v_act_opacities, float reg_s_k, float reg_o_k,
+                                 float* v_scales, float* v_opacities);
+// *out = g with its scales and opacities replaced by their activated copies in the ctx's scratch
+int st3r_activated_params(st3r_ctx* ctx, hipStream_t s, const GsParams& g, double* reg_sums, GsParams* out);
+
 // ---- gs_intrinsics.hip ----
 // the rows of the registered intrinsics gradient [C,4] of the C views at `gt`; NULL: none applies
 float* st3r_intrinsics_grad_for(st3r_ctx* ctx, const float* gt, int C, int H, int W);

@@ -212,6 +212,9 @@ class ShardedTrainer:
     def __init__(self, ctx, params, n_total, w2c_all, Ks_all, gt_local, W, H, rank, world, lr=1e-3,
                  ssim_fac=0.2, opac_fac=0.01, scale_fac=0.01, a2a=_all_to_all, counts=None):
         from . import ops
+        if ops.get_activation(ctx):   # the shards project raw scales and opacities (ops.project_sh)
+            raise NotImplementedError("ShardedTrainer does not support activated scales and opacities: the context's "
+                                      "activation is on (ops.set_activation(ctx, False) clears it)")
         self.ops, self.ctx, self.P, self.N, self.W, self.H = ops, ctx, params, n_total, W, H
         self.rank, self.world, self.a2a = rank, world, a2a
         self.w2c, self.Ks, self.gt = w2c_all.contiguous(), Ks_all.contiguous(), gt_local

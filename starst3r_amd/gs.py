@@ -8,8 +8,13 @@ Reference quirks that are reproduced on purpose: scales/opaci
 given an optimiser but never rendered (gs.py:25,29 vs :81); colours are initialised as 1 - colour in every
 SH row (gs.py:29-31); both regularisers are added once per view (gs.py:150-152); `step` restarts at 0 on
 every run_3dgs_optim call (gs.py:143) while the Adam step counters persist.
+
+Not in the reference: scene.activations = True replaces the first quirk by the canonical 3DGS parameterisation -- the
+scales tensor holds log-scales, the opacities tensor logits, and renderer, regularisers and MCMC refinement read them the
+same way (csrc/gs_activation.hip; activate_3dgs converts a raw scene).  Off by default.
 """
 __all__ = (
+    "activate_3dgs",
     "init_3dgs",
     "render_3dgs",
     "render_3dgs_original",
@@ -113,7 +118,8 @@ class MCMCStrategy:
       step_post_backward(step, lr): inside the refine window (500 < step < 25000, every 100 steps) dead
       Gaussians are relocated onto alive ones and the set grows by 5 % up to cap_max; position noise is
       injected on every call.  Opacities/scales are read as logits/logs here while the renderer uses the
-      same tensors raw -- the reference's behaviour.
+      same tensors raw -- the reference's behaviour; with scene.activations = True the renderer
+      reads them as logits/logs too.
 
     Random draws come from a counter-based generator keyed by state["seed"] and a call counter, not from
     torch's global generator: view-sharded replicas take identical decisions with no communication."""
@@ -165,16 +171,39 @@ class MCMCStrategy:
             ops.mcmc_noise(ctx, P, lr * self.noise_lr, seed, call)
 
 
+def _activations(scene):
+    """scene.activations (absent: False): do the scales hold log-scales and the opacities logits; ValueError unless a bool"""
+    on = getattr(scene, "activations", False)
+    if not isinstance(on, bool):
+        raise ValueError(f"scene.activations is True or False, got {on!r}")
+    return on
+
+
 def init_3dgs(scene, init_scale=3e-3, lr=1e-3):
-    """Initialize 3DGS splats and optims from Mast3r dense points (reference gs.py:14-45)."""
+    """Initialize 3DGS splats and optims from Mast3r dense points (reference gs.py:14-45).
+
+    With scene.activations = True (not in the reference) the scales are log(init_scale) and the opacities
+    logit(scene.init_opacity) -- init_opacity a setting of the scene, default 0.1 as in gsplat's trainer; an init_scale
+    <= 0 or an init_opacity outside (0, 1) raises ValueError before anything is allocated.  Everything else is as without."""
+    scale_0, opacity_0 = init_scale, 1.0
+    if _activations(scene):
+        p = getattr(scene, "init_opacity", 0.1)
+        if isinstance(p, bool) or not isinstance(p, (int, float, np.floating, np.integer)) or not 0.0 < float(p) < 1.0:
+            raise ValueError(f"scene.init_opacity is a float in (0, 1), got {p!r}")
+        if isinstance(init_scale, bool) or not isinstance(init_scale, (int, float, np.floating, np.integer)) or \
+                not (float(init_scale) > 0.0 and np.isfinite(float(init_scale))):
+            raise ValueError(f"scene.activations = True stores log(init_scale): init_scale must be a finite float > 0, "
+                             f"got {init_scale!r}")
+        scale_0 = float(np.log(np.float64(init_scale)))
+        opacity_0 = float(np.log(np.float64(p)) - np.log1p(-np.float64(p)))
     pts = scene.dense_pts_flat
     colors = scene.dense_cols_flat
     n = pts.shape[0]
     g = {
         "means": pts.clone().float(),
-        "scales": torch.full_like(pts, init_scale, dtype=torch.float32),
+        "scales": torch.full_like(pts, scale_0, dtype=torch.float32),
         "quats": torch.zeros(n, 4),
-        "opacities": torch.ones(n),
+        "opacities": torch.full((n,), opacity_0),
         "sh0": torch.zeros(n, 1, 3),
         "shN": torch.zeros(n, 24, 3),
     }
@@ -192,7 +221,47 @@ def init_3dgs(scene, init_scale=3e-3, lr=1e-3):
     scene._gt_dev = None
 
 
+def activate_3dgs(scene, eps=1e-4):
+    """Convert a raw scene (scales and opacities rendered as they are) to the canonical parameterisation in place:
+    scales <- log(max(|s|, 1e-30)) (the covariance only ever saw s^2), opacities <- logit(clamp(o, eps, 1 - eps)), both
+    formed in float64; scene.activations = True.  The Adam moments of the two blocks are zeroed -- the parameter space
+    changed -- while the other blocks' moments and the step counter stay.  The render of the converted scene is the raw
+    scene's wherever its opacities lay in [eps, 1 - eps].  ValueError on a scene that is activated already."""
+    if _activations(scene):
+        raise ValueError("scene.activations is True already: the scales are log-scales and the opacities logits")
+    if not 0.0 < float(eps) < 0.5:
+        raise ValueError(f"eps is a float in (0, 0.5), got {eps!r}")
+    g, st = scene.gaussians, scene._gs_optim
+    with torch.no_grad():
+        s = g["scales"].data.double().abs().clamp(min=1e-30)
+        g["scales"].data.copy_(torch.log(s))
+        o = g["opacities"].data.double().clamp(float(eps), 1.0 - float(eps))
+        g["opacities"].data.copy_(torch.log(o) - torch.log1p(-o))
+        for key in ("scales", "opacities"):
+            st.m[st.block_slice(key)] = 0.0
+            st.v[st.block_slice(key)] = 0.0
+    scene.activations = True
+
+
 RENDER_MODES = ("RGB", "D", "ED", "RGB+D", "RGB+ED")   # gsplat.rasterization's render_mode
+
+
+class _Activate(torch.autograd.Function):
+    """S = exp(scales), O = sigmoid(opacities) in front of _Rasterize (st3r_param_activate / st3r_param_activate_bwd):
+    differentiable into the log-scales and the logits; the backward reads the stored S and O."""
+
+    @staticmethod
+    def forward(fctx, scales, opacities, ctx):
+        S, O, _ = ops.param_activate(ctx, scales.detach().contiguous(), opacities.detach().contiguous())
+        fctx.save_for_backward(S, O)
+        fctx.ctx = ctx
+        return S, O
+
+    @staticmethod
+    def backward(fctx, v_S, v_O):
+        S, O = fctx.saved_tensors
+        v_s, v_o = ops.param_activate_bwd(fctx.ctx, S, O, v_S.contiguous().float(), v_O.contiguous().float())
+        return v_s, v_o, None
 
 
 class _Rasterize(torch.autograd.Function):
@@ -339,9 +408,14 @@ def render_3dgs(scene, w2c: torch.Tensor, intrinsics: torch.Tensor, width: int, 
     scene.intrinsics_grad (not in the reference; gsplat returns no such gradient; a setting of the scene, default False,
     because the argument list above is the boundary users program against): True makes the backward pass return
     d loss / d intrinsics as well when `intrinsics` requires a gradient -- (N,3,3), non-zero at fx, fy, cx, cy -- in every
-    render_mode; with False no kernel for it runs and intrinsics.grad stays None."""
+    render_mode; with False no kernel for it runs and intrinsics.grad stays None.
+    scene.activations (not in the reference; a setting of the scene, default False; anything but a bool raises ValueError):
+    True reads scene.gaussians["scales"] as log-scales and ["opacities"] as logits -- the render sees exp and sigmoid of
+    them (st3r_param_activate) in every render_mode and with every option above, back-propagates into the logs and logits,
+    and info["opacities"] holds the activated values, as in gsplat."""
     if render_mode not in RENDER_MODES:
         raise ValueError(f"render_mode must be one of {RENDER_MODES}, got {render_mode!r}")
+    activated = _activations(scene)
     backgrounds = _render_backgrounds(scene, w2c.shape[0], render_mode)
     if exposure is not None:
         _check_render_exposure(exposure, w2c.shape[0], render_mode)
@@ -352,7 +426,8 @@ def render_3dgs(scene, w2c: torch.Tensor, intrinsics: torch.Tensor, width: int, 
         exposure = exposure.to(scene.device, torch.float32)
     if backgrounds is not None:
         backgrounds = backgrounds.to(scene.device, torch.float32)
-    out = _Rasterize.apply(g["means"], g["quats"], g["scales"], g["opacities"], g["shN"], w2c, Ks, width, height, ctx,
+    scales, opacities = _Activate.apply(g["scales"], g["opacities"], ctx) if activated else (g["scales"], g["opacities"])
+    out = _Rasterize.apply(g["means"], g["quats"], scales, opacities, g["shN"], w2c, Ks, width, height, ctx,
                            render_mode != "RGB", bool(getattr(scene, "intrinsics_grad", False)))
     if render_mode == "RGB":
         rgb, alpha = out
@@ -837,6 +912,26 @@ class _AlphaMasks(_PerViewOption):
         ops.set_alpha_target(c.ctx, None, None, None)
 
 
+class _Activations(_PerViewOption):
+    """scene.activations: the ctx reads the scales as log-scales and the opacities as logits for the duration of the call.
+    No per-view data, but the same life cycle: refused like the per-view options, set where they register, cleared where
+    they clear."""
+    spelled, schedule = "scene.activations", False
+
+    @classmethod
+    def when_on(cls, scene, enable_pruning):
+        if not _activations(scene):
+            return None
+        _single_replica_only(cls.spelled, scene, enable_pruning)
+        return cls()
+
+    def register(self, c):
+        ops.set_activation(c.ctx, True)
+
+    def clear(self, c):
+        ops.set_activation(c.ctx, False)
+
+
 def _iterations(iters, verbose):
     """range(iters), with a progress bar when verbose"""
     if verbose:
@@ -961,7 +1056,16 @@ def run_3dgs_optim(
     are cached and keyed like the loss masks'; they work together with pose_lr, depth_fac, exposure_lr, scene.intrinsics_lr,
     scene.loss_masks and enable_pruning; single process, Gaussians replicated only.  With both off nothing about the call
     changes and nothing is registered.
+
+    scene.activations (not in the reference; a setting of the scene, default False; anything but a bool raises ValueError):
+    True trains log-scales and logits -- the fused step renders exp(scales) and sigmoid(opacities), the regularisers are the
+    reference's, loss_opacity_fac * mean(sigmoid(opacities)) and loss_scale_fac * mean(exp(scales)) once per view, now
+    functions of what is rendered, and the MCMC refinement of enable_pruning reads the tensors the same way as the renderer.
+    Adam, the moments and their layout do not change.  init_3dgs under the setting, or activate_3dgs on a raw scene, produce
+    such tensors.  Works together with every option above and enable_pruning; single process, Gaussians replicated only.
+    With the setting off nothing about the call changes.
     """
+    activations = _Activations.when_on(scene, enable_pruning)   # (its check comes first)
     masks = _LossMasks.when_on(scene, enable_pruning, getattr(scene, "loss_masks", None))   # (its checks come first)
     backgrounds = _Backgrounds.when_on(scene, enable_pruning, getattr(scene, "backgrounds", None))
     alphas = _AlphaMasks.when_on(scene, enable_pruning, getattr(scene, "alpha_fac", 0.0), getattr(scene, "alpha_masks", None),
@@ -971,7 +1075,7 @@ def run_3dgs_optim(
     exposures = _Exposures.when_on(scene, enable_pruning, exposure_lr, exposure_freeze)
     intrinsics = _Intrinsics.when_on(scene, enable_pruning, getattr(scene, "intrinsics_lr", 0.0))
     # in this order at every hook: checks (above), set-up, registration, clearing, behind the step, finish
-    options = [o for o in (depth, poses, exposures, intrinsics, masks, backgrounds, alphas) if o is not None]
+    options = [o for o in (depth, poses, exposures, intrinsics, masks, backgrounds, alphas, activations) if o is not None]
     counters = [o.counter for o in options if o.counter]
     height, width = scene.imgs[0].shape[:2]
     ctx = ops.get_context(scene.device)
@@ -1135,6 +1239,9 @@ def _run_3dgs_optim_sharded(scene, iters, ssim_fac, opac_fac, scale_fac, verbose
     the replicated draw); on a refinement step the shards are gathered, relocate / grow run on the full tensors --
     identically on every rank, like in the replicated layout -- and the grown set is sharded again (balanced, sizes
     differing by at most one).  Between refinement steps nothing is replicated."""
+    if _activations(scene):   # (run_3dgs_optim has refused it already: a direct call)
+        raise NotImplementedError("scene.activations != 0 is supported in a single process with replicated Gaussians only "
+                                  "(the Gaussian-sharded loop projects raw scales and opacities)")
     height, width = scene.imgs[0].shape[:2]
     ctx = ops.get_context(scene.device)
     st = scene._gs_optim

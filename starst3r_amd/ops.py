@@ -475,6 +475,60 @@ def set_alpha_target(ctx, gt, target, weight, alpha_fac=1.0):
                                   for t in (target, weight)), float(alpha_fac))
 
 
+def _activation_shapes(scales, **others):
+    """N of scales [N,3]; ValueError unless every named tensor has scales' shape or, for a name ending in `opacities`, [N]
+    -- float32 all of them"""
+    if scales.dim() != 2 or scales.shape[1] != 3 or scales.dtype != torch.float32:
+        raise ValueError(f"expected float32 scales [N,3], got {scales.dtype} {tuple(scales.shape)}")
+    N = scales.shape[0]
+    for name, t in others.items():
+        want = (N,) if name.endswith("opacities") else (N, 3)
+        if t is not None and (tuple(t.shape) != want or t.dtype != torch.float32):
+            raise ValueError(f"expected float32 {name} {want}, got {t.dtype} {tuple(t.shape)}")
+    return N
+
+
+def param_activate(ctx, scales, opacities, act_scales=None, act_opacities=None, want_sums=False):
+    """exp(scales) [N,3] and sigmoid(opacities) [N] of log-scales and logits (st3r_param_activate).  want_sums: also
+    float64 [2] = (sum sigmoid, sum exp) of the stored float32 values.  Returns (act_scales, act_opacities, sums or None)."""
+    N = _activation_shapes(scales, opacities=opacities, act_scales=act_scales, act_opacities=act_opacities)
+    act_scales = torch.empty_like(scales) if act_scales is None else act_scales
+    act_opacities = torch.empty_like(opacities) if act_opacities is None else act_opacities
+    sums = torch.empty(2, dtype=torch.float64, device=scales.device) if want_sums else None
+    _lib.check(_lib.lib().st3r_param_activate(ctx.handle, _stream(), N, _p(scales), _p(opacities), _p(act_scales),
+                                              _p(act_opacities), _p(sums, torch.float64)))
+    return act_scales, act_opacities, sums
+
+
+def param_activate_bwd(ctx, act_scales, act_opacities, v_act_scales, v_act_opacities, reg_s_k=0.0, reg_o_k=0.0,
+                       v_scales=None, v_opacities=None):
+    """The chain rule of param_activate on its stored outputs: v_scales = (v_act_scales + reg_s_k) * act_scales,
+    v_opacities = (v_act_opacities + reg_o_k) * act_opacities * (1 - act_opacities) (st3r_param_activate_bwd).  The
+    outputs may be v_act_scales / v_act_opacities themselves (in place).  Returns (v_scales, v_opacities)."""
+    N = _activation_shapes(act_scales, act_opacities=act_opacities, v_act_scales=v_act_scales,
+                           v_act_opacities=v_act_opacities, v_scales=v_scales, v_opacities=v_opacities)
+    v_scales = torch.empty_like(act_scales) if v_scales is None else v_scales
+    v_opacities = torch.empty_like(act_opacities) if v_opacities is None else v_opacities
+    _lib.check(_lib.lib().st3r_param_activate_bwd(ctx.handle, _stream(), N, _p(act_scales), _p(act_opacities),
+                                                  _p(v_act_scales), _p(v_act_opacities), float(reg_s_k), float(reg_o_k),
+                                                  _p(v_scales), _p(v_opacities)))
+    return v_scales, v_opacities
+
+
+def set_activation(ctx, on):
+    """Whether train_fwd_bwd, train_step, train_step_poses and render read `scales` as log-scales and `opacities` as logits
+    from now on (a setting of the ctx, st3r_ctx_set_activation).  Returns the previous setting."""
+    prev = get_activation(ctx)
+    _lib.check(_lib.lib().st3r_ctx_set_activation(ctx.handle, 1 if on else 0))
+    return prev
+
+
+def get_activation(ctx):
+    on = C.c_int(-1)
+    _lib.check(_lib.lib().st3r_ctx_get_activation(ctx.handle, C.byref(on)))
+    return bool(on.value)
+
+
 def intrinsics_adam_step(ctx, Ks, v_Ks, k_m, k_v, lr, b1, b2, eps, step, mask, W, H, tie_focal=True, opt_pp=False):
     """One Adam step on the intrinsics Ks [C,3,3], in place, from v_Ks [C,4] = d loss / d (fx, fy, cx, cy); moments
     k_m / k_v [4C]; the parameters are (log fx, log fy, cx / W, cy / H) (st3r_intrinsics_adam_step).  tie_focal: one

@@ -40,6 +40,11 @@ class Scene:
         self.intrinsics_tie_focal = True
         self.intrinsics_opt_pp = False
         self.intrinsics_grad = False
+        # not in the reference: the canonical 3DGS parameterisation (gs.py).  activations = True: gaussians["scales"] holds
+        # log-scales and gaussians["opacities"] logits, for init_3dgs, the render calls, run_3dgs_optim and the MCMC
+        # refinement alike (activate_3dgs converts a raw scene); init_opacity: what init_3dgs starts from under it
+        self.activations = False
+        self.init_opacity = 0.1
         self.optim_params = None
         # declared by the reference but never written (scene.py:42-45,74-77); the names in use are the ones
         # init_3dgs sets: gaussians, optimizers, ssim, strategy, strategy_state (gs.py:20,37,39,43,45)
@@ -99,6 +104,9 @@ class Scene:
 
     def init_3dgs(self, init_scale=3e-3, lr=1e-3):
         _gs.init_3dgs(self, init_scale, lr)
+
+    def activate_3dgs(self, eps=1e-4):
+        _gs.activate_3dgs(self, eps)
 
     def render_3dgs(self, w2c, intrinsics, width, height, render_mode="RGB", exposure=None):
         if exposure is not None:
