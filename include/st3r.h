@@ -84,6 +84,10 @@ int st3r_ctx_set_profiling(st3r_ctx* ctx, int enable);
  * bit 2 (4): the training calls' level-1 sort on (camera | depth) keys in four passes instead of per-camera segments.
  * (the other bits: csrc/common.h, st3r_ctx::debug_flags) */
 int st3r_ctx_set_debug(st3r_ctx* ctx, int flags);
+/* test hook: the generation stamps of the backward calls' per-(record, tile) slots (colour / depth).  The NEXT backward
+ * call stamps its slots with value + 1, or restarts at 1 over zeroed slots once the counter has reached 2 147 483 000.
+ * A negative value leaves that counter alone; values above 2 147 483 000 are refused.  Launches nothing. */
+int st3r_ctx_debug_set_stamps(st3r_ctx* ctx, int colour, int depth);
 /* Waits for the record count of the last asynchronous training step (st3r_gs_train_fwd_bwd / st3r_gs_train_step with
  * stats_host == NULL) and reports it like the next training call would: ST3R_ERR_CAPACITY if that step outgrew its
  * buffers (its Adam update was then skipped on the device: repeat the step).  For the end of a training loop

@@ -24,6 +24,7 @@ SIGNATURES = {
     "st3r_ctx_peek": [vp, vp, i32, vp, i64],
     "st3r_ctx_set_profiling": [vp, i32],
     "st3r_ctx_set_debug": [vp, i32],
+    "st3r_ctx_debug_set_stamps": [vp, i32, i32],
     "st3r_ctx_settle": [vp],
     "st3r_ctx_release_scratch": [vp],
     "st3r_ctx_get_stage_ms": [vp, C.POINTER(f64), C.POINTER(i64)],

@@ -159,6 +159,15 @@ ST3R_EXPORT int st3r_ctx_set_debug(st3r_ctx* ctx, int flags) {
     return ST3R_OK;
 }
 
+// test hook: where the stamp counters of the backward slots stand (blend_common.h: stamped_slots), so that a test can put a
+// context next to the restart without two billion calls.  No kernel reads these but through the next call's arguments.
+ST3R_EXPORT int st3r_ctx_debug_set_stamps(st3r_ctx* ctx, int colour, int depth) {
+    ARG_CHECK(ctx && colour <= 2147483000 && depth <= 2147483000);
+    if (colour >= 0) ctx->bwd_stamp = colour;
+    if (depth >= 0) ctx->depth_stamp = depth;
+    return ST3R_OK;
+}
+
 ST3R_EXPORT int st3r_ctx_set_profiling(st3r_ctx* ctx, int enable) {
     ARG_CHECK(ctx && enable >= 0 && enable < 2 + STG_COUNT);
     if (enable && !ctx->prof_ev[0][0][0]) {

@@ -771,6 +771,12 @@ def set_debug(ctx, flags):
     _lib.check(_lib.lib().st3r_ctx_set_debug(ctx.handle, int(flags)))
 
 
+def debug_set_stamps(ctx, colour=-1, depth=-1):
+    """tests only: where the stamp counters of the colour / depth backward slots stand (st3r_ctx_debug_set_stamps); a
+    negative value leaves that counter alone."""
+    _lib.check(_lib.lib().st3r_ctx_debug_set_stamps(ctx.handle, int(colour), int(depth)))
+
+
 STAGES = ("project", "scan", "emit", "sort", "offsets", "blend_fwd", "loss", "blend_bwd", "project_bwd", "adam",
           "sort_depth")
 
