@@ -410,6 +410,43 @@ int st3r_param_activate_bwd(st3r_ctx* ctx, void* stream, int N, const float* act
 int st3r_ctx_set_activation(st3r_ctx* ctx, int on);
 int st3r_ctx_get_activation(st3r_ctx* ctx, int* on);
 
+/* ---- Spherical harmonics of degree 0 to 3 (csrc/project_common.h) ----
+ * The SH degree as a setting of the context, like the activation; a context starts at (1, 1, NULL) and the call launches
+ * nothing.  0 <= active_degree <= degree <= 3, v_sh_high = NULL for degree <= 1, otherwise ST3R_ERR_INVALID.  With
+ * u = normalise(mean - campos) = (x, y, z) the colour is clamp_min(sum_i B_i(u) k_i + 0.5, 0) over the rows
+ * i < K = (active_degree + 1)^2 of a Gaussian, at floats 0 .. 3K - 1 of sh + g * sh_stride:
+ *   B_0 = 0.2820947917738781         B_1, B_2, B_3 = 0.48860251190292 (-y, z, -x)
+ *   B_4 .. B_8  = 1.0925484305920792 xy, -1.0925484305920792 yz, 0.31539156525252005 (2zz - xx - yy),
+ *                 -1.0925484305920792 xz, 0.5462742152960396 (xx - yy)
+ *   B_9 .. B_15 = -0.5900435899266435 y(3xx - yy), 2.890611442640554 xyz, -0.4570457994644658 y(4zz - xx - yy),
+ *                 0.3731763325901154 z(2zz - 3xx - 3yy), -0.4570457994644658 x(4zz - xx - yy),
+ *                 1.445305721320277 z(xx - yy), -0.5900435899266435 x(xx - 3yy)
+ * While the setting is not (1, 1, NULL), st3r_gs_project_sh, st3r_gs_project_sh_bwd, st3r_gs_viewmat_bwd, st3r_gs_render
+ * and st3r_gs_train_fwd_bwd / _step / _step_poses evaluate those K rows and require
+ * sh_stride >= 3 max(4, (degree + 1)^2).  Each band is summed on its own and added to the bands below it: a Gaussian
+ * whose rows above a degree are zero renders with that degree's bits.  The backward calls decide the clamp's
+ * pass-through on the full pre-clamp value; rows 0..3 of the coefficient gradient go to the sh4 block of grads as always
+ * (rows 1..3 are zeros at active_degree 0), rows 4 .. (degree + 1)^2 - 1 to v_sh_high [N, 3 ((degree + 1)^2 - 4)]
+ * (device, the CALLER's, valid until the setting changes).  With degree >= 2 a backward call writes v_sh_high whole --
+ * zeros for the bands above active_degree and for culled Gaussians -- or, where it adds to grads (a later view chunk
+ * of a training call), adds to it; v_sh_high is indexed by Gaussian, never range-major.  Sums per Gaussian in registers
+ * in camera order, no atomics: the same inputs give the same bits.  A backward call with degree >= 2 and
+ * v_sh_high == NULL returns ST3R_ERR_INVALID; forward-only calls do not need it.  At (1, 1, NULL) every call launches
+ * the kernels it launched before.  With a communicator attached the training calls return ST3R_ERR_INVALID while the
+ * setting is not the default; st3r_gs_raster_train takes records and is not concerned.  st3r_ctx_get_sh_degree reads the
+ * three values back. */
+int st3r_ctx_set_sh_degree(st3r_ctx* ctx, int degree, int active_degree, float* v_sh_high);
+int st3r_ctx_get_sh_degree(st3r_ctx* ctx, int* degree, int* active_degree, float** v_sh_high);
+
+/* One Adam step on the SH rows above the sh4 block: floats 12 .. 3K - 1, K = (degree + 1)^2, degree 2 or 3, of every row
+ * of sh (in/out, sh_stride >= 3K), from v_sh_high [N, 3 (K - 4)]; moments m, v [N, 3 (K - 4)] float32 (in/out).  The
+ * arithmetic of st3r_adam_step per scalar, bias corrected, no weight decay.  The update is guarded on the device by the
+ * record count of a training step still in flight, as st3r_exposure_adam_step is: a step that outgrew its buffers moves
+ * no coefficient and no moment. */
+int st3r_sh_high_adam_step(st3r_ctx* ctx, void* stream, int N, float* sh, int sh_stride, int degree,
+                           const float* v_sh_high, float* m, float* v, double lr, double beta1, double beta2, double eps,
+                           int step);
+
 /* Gradient of the render loss with respect to each camera's intrinsics, from the per-pair gradients v_splats of
  * st3r_gs_blend_bwd (floats 0-1 and 3-5; colour and depth do not depend on K): v_Ks [C,4] = d loss / d (fx, fy, cx, cy),
  * written whole.  Per visible pair (radius > 0), in float32, with p = R m + t = (x, y, z), the projection Jacobian

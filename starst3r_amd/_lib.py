@@ -63,6 +63,9 @@ SIGNATURES = {
     "st3r_param_activate_bwd": [vp, vp, i32, vp, vp, vp, vp, f32, f32, vp, vp],
     "st3r_ctx_set_activation": [vp, i32],
     "st3r_ctx_get_activation": [vp, C.POINTER(i32)],
+    "st3r_ctx_set_sh_degree": [vp, i32, i32, vp],
+    "st3r_ctx_get_sh_degree": [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(vp)],
+    "st3r_sh_high_adam_step": [vp, vp, i32, vp, i32, i32, vp, vp, vp, f64, f64, f64, f64, i32],
     "st3r_gs_intrinsics_bwd": [vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, i32, f32, vp, vp, vp],
     "st3r_intrinsics_adam_step": [vp, vp, i32, vp, vp, vp, vp, f64, f64, f64, f64, i32, vp, i32, i32, i32],
     "st3r_ctx_set_intrinsics_grad": [vp, vp, vp, i32, i32, i32],

@@ -233,6 +233,44 @@ ST3R_EXPORT int st3r_adam_step(st3r_ctx* ctx, void* stream, int N, float* means,
     return rc;
 }
 
+// The SH rows above the sh4 block (st3r_ctx_set_sh_degree): floats 12 .. 12 + H - 1 of every row of sh, gradients and
+// moments [N, H].  k_adam's arithmetic per scalar, behind the same guard.
+__global__ __launch_bounds__(256) void k_sh_high_adam(int64_t N, int H, float* __restrict__ sh, int sh_stride,
+                                                      const float* __restrict__ grads, float* __restrict__ m,
+                                                      float* __restrict__ v, AdamK k,
+                                                      const int32_t* __restrict__ count_dev, uint32_t count_cap) {
+    if (ADAM_SKIP(count_dev, count_cap, (const int32_t*)nullptr)) return;
+    const int64_t total = N * H;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+        const int64_t g = i / H;
+        float* p = sh + g * sh_stride + 12 + (i - g * H);
+        const float gi = grads[i];
+        const float mi = fmaf(k.w1, gi - m[i], m[i]);
+        const float vi = v[i] * k.b2 + (k.w2 * gi) * gi;
+        m[i] = mi; v[i] = vi;
+        const float denom = sqrtf(vi) / k.bc2_sqrt + k.eps;
+        *p = *p - k.step_size * (mi / denom);
+    }
+}
+
+ST3R_EXPORT int st3r_sh_high_adam_step(st3r_ctx* ctx, void* stream, int N, float* sh, int sh_stride, int degree,
+                                       const float* v_sh_high, float* m, float* v, double lr, double beta1, double beta2,
+                                       double eps, int step) {
+    ARG_CHECK(ctx && N >= 0 && step >= 1 && degree >= 2 && degree <= 3);
+    const int H = 3 * ((degree + 1) * (degree + 1) - 4);
+    ARG_CHECK(sh_stride >= 12 + H && sh && v_sh_high && m && v);
+    if (N == 0) return ST3R_OK;
+    const int32_t* count_dev; uint32_t count_cap;
+    st3r_adam_guard(ctx, &count_dev, &count_cap);
+    int blocks = ceil_div((int64_t)N * H, 256);
+    if (blocks > 256 * 16) blocks = 256 * 16;
+    hipLaunchKernelGGL(k_sh_high_adam, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (int64_t)N, H, sh, sh_stride,
+                       v_sh_high, m, v, adam_constants(lr, beta1, beta2, eps, step), count_dev, count_cap);
+    LAUNCH_CHECK();
+    return ST3R_OK;
+}
+
 ST3R_EXPORT int st3r_adam_step_range(st3r_ctx* ctx, void* stream, int N, float* means, float* quats, float* scales,
                                      float* opacities, float* sh, int sh_stride, const float* grads, float* m, float* v,
                                      double lr, double beta1, double beta2, double eps, int step, int64_t i0, int64_t i1,

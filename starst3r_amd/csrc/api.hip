@@ -26,6 +26,7 @@ ST3R_EXPORT int st3r_ctx_create(int device, st3r_ctx** out) {
     if (!c) { st3r_set_error("out of host memory"); return ST3R_ERR_NOMEM; }
     memset(c, 0, sizeof(*c));
     c->device = device;
+    c->sh_degree = c->sh_active = 1;
     hipError_t e = hipHostMalloc((void**)&c->pinned, 64 * sizeof(int64_t), hipHostMallocDefault);
     if (e != hipSuccess) { delete c; st3r_set_error("hipHostMalloc: %s", hipGetErrorString(e)); return ST3R_ERR_HIP; }
     *out = c;
@@ -156,6 +157,20 @@ ST3R_EXPORT int st3r_ctx_set_debug(st3r_ctx* ctx, int flags) {
         ctx->scan_gen = (ctx->scan_gen & 1u) ? 0x3FFDu : 0x3FFEu;
         ctx->scan_gen_b = (ctx->scan_gen_b & 1u) ? 0x3FFDu : 0x3FFEu;
     }
+    return ST3R_OK;
+}
+
+// The SH degree as a setting of the context (project_common.h); launches nothing.
+ST3R_EXPORT int st3r_ctx_set_sh_degree(st3r_ctx* ctx, int degree, int active_degree, float* v_sh_high) {
+    ARG_CHECK(ctx && 0 <= active_degree && active_degree <= degree && degree <= 3);
+    ARG_CHECK(degree >= 2 || !v_sh_high);
+    ctx->sh_degree = degree; ctx->sh_active = active_degree; ctx->sh_v_high = v_sh_high;
+    return ST3R_OK;
+}
+
+ST3R_EXPORT int st3r_ctx_get_sh_degree(st3r_ctx* ctx, int* degree, int* active_degree, float** v_sh_high) {
+    ARG_CHECK(ctx && degree && active_degree && v_sh_high);
+    *degree = ctx->sh_degree; *active_degree = ctx->sh_active; *v_sh_high = ctx->sh_v_high;
     return ST3R_OK;
 }
 

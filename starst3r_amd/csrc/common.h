@@ -186,6 +186,9 @@ struct st3r_ctx {
     // activated parameters (st3r_ctx_set_activation, gs_activation.hip): the fused steps and st3r_gs_render read the scales
     // as logs and the opacities as logits
     int activation;
+    // SH degree (st3r_ctx_set_sh_degree, project_common.h): the rows the tensor holds, the rows evaluated, and where the
+    // gradients of the rows 4.. go (caller-owned); (1, 1, NULL) unless set
+    int sh_degree, sh_active; float* sh_v_high;
     int bwd_stamp;  // generation stamp of the per-(record, tile) partial-gradient slots
     int depth_stamp;  // the same for the depth backward's slots (SLOT_VTILE_DEPTH)
     uint32_t scan_gen;   // single-pass scan (gs_isect.hip): generation of its status words

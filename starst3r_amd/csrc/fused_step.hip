@@ -582,6 +582,15 @@ int st3r_train_fwd_bwd_impl(st3r_ctx* ctx, hipStream_t s, const GsParams& g, con
         ARENA_GET(SLOT_ATARGET_SUMS, double, (size_t)C, as);
         at_sums = as;
     }
+    // an SH degree other than the default (st3r_ctx_set_sh_degree): the same rule
+    if (ctx->comm && !(ctx->sh_degree == 1 && ctx->sh_active == 1)) {
+        st3r_set_error("the SH degree is set and a communicator is attached -- SH degrees other than 1 are not supported "
+                       "in view-sharded training (restore it with st3r_ctx_set_sh_degree(ctx, 1, 1, NULL))");
+        return ST3R_ERR_INVALID;
+    }
+    GsParams gsh = g;
+    rc = st3r_sh_setting(ctx, &gsh, true);
+    if (rc) return rc;
     // activated parameters (st3r_ctx_set_activation): the same rule
     const bool activated = ctx->activation != 0;
     if (activated && ctx->comm) {
@@ -596,10 +605,10 @@ int st3r_train_fwd_bwd_impl(st3r_ctx* ctx, hipStream_t s, const GsParams& g, con
     // both regulariser factors 0 -- every kernel sees activated geometry, unchanged.  The sums the projection still
     // leaves in reg_sums[0..1] are then of the wrong tensors and are not used: the activation's own two, next to
     // reg_sums, take their place in the loss.
-    GsParams ga = g;
+    GsParams ga = gsh;
     double* const act_sums = small + 2 * C + 8;   // [2]: sum sigmoid(o), sum exp(s)
     if (activated) {
-        rc = st3r_activated_params(ctx, s, g, act_sums, &ga);
+        rc = st3r_activated_params(ctx, s, gsh, act_sums, &ga);
         if (rc) return rc;
     }
     // the chunk count sticks to the context; debug flag 32 starts at two chunks (tests)
@@ -695,6 +704,8 @@ ST3R_EXPORT int st3r_gs_render(st3r_ctx* ctx, void* stream, int N, int C, const 
     int rc = st3r_count_settle(ctx);
     if (rc) return rc;
     GsParams g{N, means, quats, scales, opacities, sh, sh_stride};
+    rc = st3r_sh_setting(ctx, &g, false);
+    if (rc) return rc;
     if (ctx->activation) {   // log-scales and logits (st3r_ctx_set_activation): render their activated copies
         rc = st3r_activated_params(ctx, s, g, nullptr, &g);
         if (rc) return rc;

@@ -32,6 +32,8 @@ __device__ __forceinline__ void block_sum_pose(double (&v)[POSE_VALS], double* r
     __syncthreads();
 }
 
+// DEG: the SH degree in use (st3r_ctx_set_sh_degree); 1 is the kernel as it always was
+template <int DEG>
 __global__ __launch_bounds__(256) void k_viewmat_bwd_part(
     int N, const float* __restrict__ means, const float* __restrict__ quats, const float* __restrict__ scales,
     const float* __restrict__ sh, int sh_stride, const float* __restrict__ viewmats, const float* __restrict__ Ks,
@@ -57,10 +59,11 @@ __global__ __launch_bounds__(256) void k_viewmat_bwd_part(
         const float mx = means[3 * g], my = means[3 * g + 1], mz = means[3 * g + 2];
         float qw = quats[4 * g], qx = quats[4 * g + 1], qy = quats[4 * g + 2], qz = quats[4 * g + 3];
         const float sc[3] = {scales[3 * g], scales[3 * g + 1], scales[3 * g + 2]};
-        float k[12];
+        constexpr int KF = 3 * SH_ROWS(DEG);   // coefficient floats read per Gaussian
+        float k[KF];
         const float* kp = sh + (int64_t)g * sh_stride;
 #pragma unroll
-        for (int i = 0; i < 12; ++i) k[i] = kp[i];
+        for (int i = 0; i < KF; ++i) k[i] = kp[i];
         // world covariance Sigma = M M^T, M = Rq diag(s)
         const float inv_norm = 1.0f / sqrtf(((qw * qw + qx * qx) + qy * qy) + qz * qz);
         qw *= inv_norm; qx *= inv_norm; qy *= inv_norm; qz *= inv_norm;
@@ -84,7 +87,7 @@ __global__ __launch_bounds__(256) void k_viewmat_bwd_part(
             cov[5] = M[6] * M[6] + M[7] * M[7] + M[8] * M[8];
         }
         // ---- SH backward: v_d, the gradient of the unnormalised direction d = m - campos ----
-        {
+        if constexpr (DEG == 1) {
             float dx = mx - campos[3 * c], dy = my - campos[3 * c + 1], dz = mz - campos[3 * c + 2];
             float nrm = sqrtf(dx * dx + dy * dy + dz * dz);
             float inrm = 1.0f / nrm;
@@ -101,6 +104,19 @@ __global__ __launch_bounds__(256) void k_viewmat_bwd_part(
                 vdy += -SH_C1 * k[3 + ch] * vc;
                 vdz += SH_C1 * k[6 + ch] * vc;
             }
+            float dotp = vdx * ux + vdy * uy + vdz * uz;
+            acc[12] = -((vdx - dotp * ux) * inrm);
+            acc[13] = -((vdy - dotp * uy) * inrm);
+            acc[14] = -((vdz - dotp * uz) * inrm);
+        } else {
+            float dx = mx - campos[3 * c], dy = my - campos[3 * c + 1], dz = mz - campos[3 * c + 2];
+            float nrm = sqrtf(dx * dx + dy * dy + dz * dz);
+            float inrm = 1.0f / nrm;
+            float ux = dx * inrm, uy = dy * inrm, uz = dz * inrm;
+            const float vcol[3] = {g1.z, g1.w, g2.x};
+            const float colf[3] = {r1.z, r1.w, r2.x};
+            float vdx, vdy, vdz;
+            sh_chain<DEG, false>(k, vcol, colf, ux, uy, uz, nullptr, vdx, vdy, vdz);
             float dotp = vdx * ux + vdy * uy + vdz * uz;
             acc[12] = -((vdx - dotp * ux) * inrm);
             acc[13] = -((vdy - dotp * uy) * inrm);
@@ -220,6 +236,9 @@ ST3R_EXPORT int st3r_gs_viewmat_bwd(st3r_ctx* ctx, void* stream, int N, int C, c
                                     const float* splats, const float* v_splats, float* v_viewmats) {
     ARG_CHECK(ctx && N >= 0 && C > 0 && C <= ST3R_MAX_VIEWS && sh_stride >= 12 && width > 0 && height > 0);
     ARG_CHECK(means && quats && scales && sh && viewmats && Ks && campos && splats && v_splats && v_viewmats);
+    GsParams gp{N, means, quats, scales, nullptr, sh, sh_stride};
+    const int rc_sh = st3r_sh_setting(ctx, &gp, false);   // (reads the coefficients, writes no coefficient gradient)
+    if (rc_sh) return rc_sh;
     (void)eps2d;   // the conic in the splat records already holds it
     hipStream_t s = (hipStream_t)stream;
     const int nb = ceil_div(N, 256);
@@ -227,8 +246,16 @@ ST3R_EXPORT int st3r_gs_viewmat_bwd(st3r_ctx* ctx, void* stream, int N, int C, c
     if (nb > 0) {
         ARENA_GET(SLOT_POSE_PART, double, POSE_VALS * (size_t)nb * C, p);
         part = p;
-        hipLaunchKernelGGL(k_viewmat_bwd_part, dim3(nb, C), dim3(256), 0, s, N, means, quats, scales, sh, sh_stride,
-                           viewmats, Ks, campos, width, height, (const float4*)splats, (const float4*)v_splats, part);
+#define VIEWMAT_PART(DEG)                                                                                                  \
+    hipLaunchKernelGGL(k_viewmat_bwd_part<DEG>, dim3(nb, C), dim3(256), 0, s, N, means, quats, scales, sh, sh_stride,          \
+                       viewmats, Ks, campos, width, height, (const float4*)splats, (const float4*)v_splats, part)
+        switch (gp.sh_active) {
+            case 0: VIEWMAT_PART(0); break;
+            case 2: VIEWMAT_PART(2); break;
+            case 3: VIEWMAT_PART(3); break;
+            default: VIEWMAT_PART(1); break;
+        }
+#undef VIEWMAT_PART
         LAUNCH_CHECK();
     }
     hipLaunchKernelGGL(k_viewmat_bwd_finish, dim3(C), dim3(256), 0, s, nb, viewmats, (const double*)part, v_viewmats);

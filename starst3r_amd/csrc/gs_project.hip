@@ -17,6 +17,8 @@ __device__ __forceinline__ float dot3f(float a0, float a1, float a2, float b0, f
     return (a0 * b0 + a1 * b1) + a2 * b2;
 }
 
+// DEG: the SH degree in use (st3r_ctx_set_sh_degree); 1 is the kernel as it always was
+template <int DEG>
 __global__ __launch_bounds__(256) void k_project_sh_fwd(
     int N, int C, const float* __restrict__ means, const float* __restrict__ quats,
     const float* __restrict__ scales, const float* __restrict__ opacities, const float* __restrict__ sh,
@@ -52,7 +54,8 @@ __global__ __launch_bounds__(256) void k_project_sh_fwd(
     const bool active = g < N;
     float mx = 0, my = 0, mz = 0, opac = 0;
     float cov0 = 0, cov1 = 0, cov2 = 0, cov3 = 0, cov4 = 0, cov5 = 0;
-    float k[12];
+    constexpr int KF = 3 * SH_ROWS(DEG);   // coefficient floats read per Gaussian
+    float k[KF];
     float reg_o = 0.f, reg_s = 0.f;
     if (active) {
         mx = means[3 * g]; my = means[3 * g + 1]; mz = means[3 * g + 2];
@@ -61,7 +64,7 @@ __global__ __launch_bounds__(256) void k_project_sh_fwd(
         float s0 = scales[3 * g], s1 = scales[3 * g + 1], s2 = scales[3 * g + 2];
         const float* kp = sh + (int64_t)g * sh_stride;
 #pragma unroll
-        for (int i = 0; i < 12; ++i) k[i] = kp[i];
+        for (int i = 0; i < KF; ++i) k[i] = kp[i];
         float n2 = ((qw * qw + qx * qx) + qy * qy) + qz * qz;
         float inv = 1.0f / sqrtf(n2);
         qw *= inv; qx *= inv; qy *= inv; qz *= inv;
@@ -164,12 +167,22 @@ __global__ __launch_bounds__(256) void k_project_sh_fwd(
             float inorm = 1.0f / sqrtf((dx * dx + dy * dy) + dz * dz);
             dx *= inorm; dy *= inorm; dz *= inorm;
             float col[3];
+            if constexpr (DEG == 1) {
 #pragma unroll
-            for (int ch = 0; ch < 3; ++ch) {
-                float r = SH_C0 * k[ch];
-                r = r + SH_C1 * ((-dy * k[3 + ch] + dz * k[6 + ch]) - dx * k[9 + ch]);
-                r = r + 0.5f;
-                col[ch] = r < 0.0f ? 0.0f : r;
+                for (int ch = 0; ch < 3; ++ch) {
+                    float r = SH_C0 * k[ch];
+                    r = r + SH_C1 * ((-dy * k[3 + ch] + dz * k[6 + ch]) - dx * k[9 + ch]);
+                    r = r + 0.5f;
+                    col[ch] = r < 0.0f ? 0.0f : r;
+                }
+            } else {
+                float b[16];
+                sh_basis_high<DEG>(dx, dy, dz, b);
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch) {
+                    const float r = sh_pre_clamp<DEG>(k, ch, dx, dy, dz, b);
+                    col[ch] = r < 0.0f ? 0.0f : r;
+                }
             }
             // tile rectangle (isect_tiles pass 1)
             tr = ref_tile_rect(m2x, m2y, radius, tile_size, tile_w, tile_h);
@@ -296,10 +309,18 @@ int st3r_project_impl(st3r_ctx* ctx, hipStream_t s, const GsParams& g, const GsV
         ARENA_GET(SLOT_KRANGE_PART, uint32_t, 2 * (size_t)grid.x, p);
         krange_part = p;
     }
-    hipLaunchKernelGGL(k_project_sh_fwd, grid, block, shmem, s, N, C, g.means, g.quats, g.scales, g.opacities, g.sh,
-                       g.sh_stride, v.viewmats, v.Ks, v.campos, width, height, tile_size, tile_w, tile_h, eps2d, near_plane, far_plane,
-                       radius_clip, (float4*)splats, tiles_per_gauss, reg_part, depth_keys, depth_vals, tight, key_base,
-                       rects, rect32, krange_part);
+#define PROJECT_FWD(DEG)                                                                                                   \
+    hipLaunchKernelGGL(k_project_sh_fwd<DEG>, grid, block, shmem, s, N, C, g.means, g.quats, g.scales, g.opacities, g.sh,      \
+                       g.sh_stride, v.viewmats, v.Ks, v.campos, width, height, tile_size, tile_w, tile_h, eps2d, near_plane,   \
+                       far_plane, radius_clip, (float4*)splats, tiles_per_gauss, reg_part, depth_keys, depth_vals, tight,      \
+                       key_base, rects, rect32, krange_part)
+    switch (g.sh_active) {   // (st3r_ctx_set_sh_degree; 1 unless the caller set it)
+        case 0: PROJECT_FWD(0); break;
+        case 2: PROJECT_FWD(2); break;
+        case 3: PROJECT_FWD(3); break;
+        default: PROJECT_FWD(1); break;
+    }
+#undef PROJECT_FWD
     if (reg_sums)
         hipLaunchKernelGGL(k_reg_reduce, dim3(1), dim3(256), 0, s, (int)grid.x, reg_part, reg_sums, reg_overwrite, zero_ptr,
                            zero_ptr ? zero_n : 0, (const uint32_t*)krange_part, krange);
@@ -317,7 +338,10 @@ ST3R_EXPORT int st3r_gs_project_sh(st3r_ctx* ctx, void* stream, int N, int C, co
                                    int32_t* tiles_per_gauss, double* reg_sums) {
     ARG_CHECK(ctx && N >= 0 && C > 0 && C <= ST3R_MAX_VIEWS && sh_stride >= 12 && width > 0 && height > 0 && tile_size > 0);
     ARG_CHECK(means && quats && scales && opacities && sh && viewmats && Ks && campos && splats && tiles_per_gauss);
-    return st3r_project_impl(ctx, (hipStream_t)stream, GsParams{N, means, quats, scales, opacities, sh, sh_stride},
+    GsParams g{N, means, quats, scales, opacities, sh, sh_stride};
+    const int rc = st3r_sh_setting(ctx, &g, false);
+    if (rc) return rc;
+    return st3r_project_impl(ctx, (hipStream_t)stream, g,
                              GsViews{C, width, height, viewmats, Ks, campos}, tile_size, eps2d, near_plane, far_plane, radius_clip, splats,
                              tiles_per_gauss, reg_sums, nullptr, nullptr, 0, 0u, nullptr, 0, 0, nullptr, 0, nullptr);
 }

@@ -16,20 +16,27 @@
 #include "stages.h"
 #include "blend_common.h"
 #include "project_common.h"
+#include <type_traits>
 
 #ifndef GATHER_WIDE_ABOVE
 #define GATHER_WIDE_ABOVE 6   // slots per pair (wave average) above which the slot gather deals its additions by item
 #endif
 
-template <bool GATHER>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k_project_sh_bwd(
+// DEG: the SH degree in use (st3r_ctx_set_sh_degree); 1 is the kernel as it always was.  DEG >= 2: the gradients of the
+// rows 4 .. SH_ROWS(DEG) - 1 go to v_sh_high (rows of hi_stride floats, by Gaussian, never range-major), under the same
+// `accumulate` rule as grads.  Those degrees hold 3 SH_ROWS(DEG) coefficients and as many sums per thread: they are not
+// held to the four waves per SIMD of the tuned degree-1 kernel.  HI: empty for DEG <= 1, whose argument list is the one it
+// always was; one ShHighOut otherwise.
+struct ShHighOut { float* v_sh_high; int hi_stride; };
+template <bool GATHER, int DEG, typename... HI>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DEG <= 1 ? 4 : 1))) void k_project_sh_bwd(
     int N, int C, const float* __restrict__ means, const float* __restrict__ quats,
     const float* __restrict__ scales, const float* __restrict__ opacities, const float* __restrict__ sh,
     int sh_stride, const float* __restrict__ viewmats, const float* __restrict__ Ks,
     const float* __restrict__ campos, int W, int H, float eps2d, const float4* __restrict__ splats,
     const float4* __restrict__ v_splats, float reg_o_k, float reg_s_k, float* __restrict__ grads, int accumulate,
     int g_begin, int g_end, int range_major, const int32_t* __restrict__ cum, const float* __restrict__ vtile, int stamp,
-    unsigned vt_cap, const uint32_t* __restrict__ touch) {
+    unsigned vt_cap, const uint32_t* __restrict__ touch, HI... hi) {
     extern __shared__ float cam[];
     constexpr int ROW = ACC_VALS;   // odd stride: rows of neighbouring slots fall into different banks
     __shared__ float sVal[GATHER ? 256 * ROW : 1];    // per wave: the current chunk of 64 slots, nine values each
@@ -60,10 +67,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
     const float opac = opacities[g];
     float qw = quats[4 * g], qx = quats[4 * g + 1], qy = quats[4 * g + 2], qz = quats[4 * g + 3];
     const float s0 = scales[3 * g], s1 = scales[3 * g + 1], s2 = scales[3 * g + 2];
-    float k[12];
+    constexpr int KF = 3 * SH_ROWS(DEG);     // coefficient floats read per Gaussian
+    constexpr int KV = KF < 12 ? 12 : KF;    // gradient sums: the sh4 block always gets its 12
+    float k[KF];
     const float* kp = sh + (int64_t)g * sh_stride;
 #pragma unroll
-    for (int i = 0; i < 12; ++i) k[i] = kp[i];
+    for (int i = 0; i < KF; ++i) k[i] = kp[i];
     const float inv_norm = 1.0f / sqrtf(((qw * qw + qx * qx) + qy * qy) + qz * qz);
     qw *= inv_norm; qx *= inv_norm; qy *= inv_norm; qz *= inv_norm;
     // rotation and M = Rq diag(s): needed for the covariance here and for the quaternion / scale chain rule after the camera
@@ -95,9 +104,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
 
     float v_mean[3] = {0, 0, 0};
     float vSw[6] = {0, 0, 0, 0, 0, 0};  // symmetric world-covariance gradient: 00 01 02 11 12 22
-    float v_k[12];
+    float v_k[KV];
 #pragma unroll
-    for (int i = 0; i < 12; ++i) v_k[i] = 0.f;
+    for (int i = 0; i < KV; ++i) v_k[i] = 0.f;
     float v_opac = 0.f;
 
     for (int c = 0; c < C; ++c) {
@@ -227,7 +236,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
         const float R[9] = {o[0], o[1], o[2], o[4], o[5], o[6], o[8], o[9], o[10]};
         v_opac += g0.z;
         // ---- SH backward ----
-        {
+        if constexpr (DEG == 1) {
             float dx = mx - o[20], dy = my - o[21], dz = mz - o[22];
             float nrm = sqrtf(dx * dx + dy * dy + dz * dz);
             float inrm = 1.0f / nrm;
@@ -249,6 +258,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
                 vdy += -SH_C1 * k[3 + ch] * vc;
                 vdz += SH_C1 * k[6 + ch] * vc;
             }
+            float dotp = vdx * ux + vdy * uy + vdz * uz;
+            v_mean[0] += (vdx - dotp * ux) * inrm;
+            v_mean[1] += (vdy - dotp * uy) * inrm;
+            v_mean[2] += (vdz - dotp * uz) * inrm;
+        } else {
+            float dx = mx - o[20], dy = my - o[21], dz = mz - o[22];
+            float nrm = sqrtf(dx * dx + dy * dy + dz * dz);
+            float inrm = 1.0f / nrm;
+            float ux = dx * inrm, uy = dy * inrm, uz = dz * inrm;
+            const float vcol[3] = {g1.z, g1.w, g2.x};
+            const float colf[3] = {r1.z, r1.w, r2.x};
+            float vdx, vdy, vdz;
+            sh_chain<DEG, true>(k, vcol, colf, ux, uy, uz, v_k, vdx, vdy, vdz);
             float dotp = vdx * ux + vdy * uy + vdz * uz;
             v_mean[0] += (vdx - dotp * ux) * inrm;
             v_mean[1] += (vdy - dotp * uy) * inrm;
@@ -370,6 +392,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
     go[gw] = v_opac;
 #pragma unroll
     for (int i = 0; i < 12; ++i) gsh[(int64_t)gw * 12 + i] = v_k[i];
+    if constexpr (DEG >= 2) {
+        const ShHighOut out = (hi, ...);
+        float* __restrict__ gh = out.v_sh_high + (int64_t)g * out.hi_stride;
+#pragma unroll
+        for (int i = 12; i < KF; ++i) gh[i - 12] = accumulate ? gh[i - 12] + v_k[i] : v_k[i];
+    }
 }
 
 int st3r_project_sh_bwd_impl(hipStream_t s, const GsParams& g, const GsViews& v, float eps2d, const float* splats,
@@ -381,16 +409,37 @@ int st3r_project_sh_bwd_impl(hipStream_t s, const GsParams& g, const GsViews& v,
     float reg_o_k = reg_views * opac_fac / (float)N;
     float reg_s_k = reg_views * scale_fac / (3.0f * (float)N);
     size_t shmem = (size_t)C * CAM_STRIDE * sizeof(float);
-    if (slots)   // fused training calls: the pair sums are gathered from the backward's slots in this kernel
-        hipLaunchKernelGGL(k_project_sh_bwd<true>, dim3(ceil_div(g_end - g_begin, 256)), dim3(256), shmem, s, N, C, g.means,
-                           g.quats, g.scales, g.opacities, g.sh, g.sh_stride, v.viewmats, v.Ks, v.campos, v.W, v.H, eps2d,
-                           (const float4*)splats, (const float4*)nullptr, reg_o_k, reg_s_k, grads, accumulate ? 1 : 0, g_begin,
-                           g_end, range_major ? 1 : 0, slots->cum, slots->vtile, slots->stamp, slots->vt_cap, slots->touch);
-    else
-        hipLaunchKernelGGL(k_project_sh_bwd<false>, dim3(ceil_div(g_end - g_begin, 256)), dim3(256), shmem, s, N, C, g.means,
-                           g.quats, g.scales, g.opacities, g.sh, g.sh_stride, v.viewmats, v.Ks, v.campos, v.W, v.H, eps2d,
-                           (const float4*)splats, (const float4*)v_splats, reg_o_k, reg_s_k, grads, accumulate ? 1 : 0, g_begin,
-                           g_end, range_major ? 1 : 0, (const int32_t*)nullptr, (const float*)nullptr, 0, 0u, (const uint32_t*)nullptr);
+    // st3r_ctx_set_sh_degree: the kernel of the degree in use writes its own rows of v_sh_high; the rows of the bands
+    // above it are zeros (a later view chunk adds to the earlier ones: nothing to add)
+    const int hi_stride = 3 * (SH_ROWS(g.sh_degree) - 4);
+    if (g.sh_degree >= 2 && g.sh_active < g.sh_degree && !accumulate)
+        HIP_TRY(hipMemsetAsync(g.v_sh_high + (size_t)g_begin * hi_stride, 0,
+                               sizeof(float) * (size_t)(g_end - g_begin) * hi_stride, s));
+    const ShHighOut out{g.v_sh_high, hi_stride};
+    // deg: the degree in use as a type; hi: nothing for degrees 0 and 1, `out` for 2 and 3.
+    // slots: the fused training calls -- the pair sums are gathered from the backward's slots in this kernel
+    auto launch = [&](auto deg, auto... hi) {
+        constexpr int DEG = decltype(deg)::value;
+        const dim3 grid(ceil_div(g_end - g_begin, 256)), block(256);
+        if (slots)
+            hipLaunchKernelGGL((k_project_sh_bwd<true, DEG, decltype(hi)...>), grid, block, shmem, s, N, C, g.means, g.quats,
+                               g.scales, g.opacities, g.sh, g.sh_stride, v.viewmats, v.Ks, v.campos, v.W, v.H, eps2d,
+                               (const float4*)splats, (const float4*)nullptr, reg_o_k, reg_s_k, grads, accumulate ? 1 : 0,
+                               g_begin, g_end, range_major ? 1 : 0, slots->cum, slots->vtile, slots->stamp, slots->vt_cap,
+                               slots->touch, hi...);
+        else
+            hipLaunchKernelGGL((k_project_sh_bwd<false, DEG, decltype(hi)...>), grid, block, shmem, s, N, C, g.means, g.quats,
+                               g.scales, g.opacities, g.sh, g.sh_stride, v.viewmats, v.Ks, v.campos, v.W, v.H, eps2d,
+                               (const float4*)splats, (const float4*)v_splats, reg_o_k, reg_s_k, grads, accumulate ? 1 : 0,
+                               g_begin, g_end, range_major ? 1 : 0, (const int32_t*)nullptr, (const float*)nullptr, 0, 0u,
+                               (const uint32_t*)nullptr, hi...);
+    };
+    switch (g.sh_active) {
+        case 0: launch(std::integral_constant<int, 0>{}); break;
+        case 2: launch(std::integral_constant<int, 2>{}, out); break;
+        case 3: launch(std::integral_constant<int, 3>{}, out); break;
+        default: launch(std::integral_constant<int, 1>{}); break;
+    }
     LAUNCH_CHECK();
     return ST3R_OK;
 }
@@ -403,7 +452,10 @@ ST3R_EXPORT int st3r_gs_project_sh_bwd(st3r_ctx* ctx, void* stream, int N, int C
                                        float opac_fac, float scale_fac, float* grads) {
     ARG_CHECK(ctx && N >= 0 && C > 0 && C <= ST3R_MAX_VIEWS && sh_stride >= 12);
     ARG_CHECK(means && quats && scales && opacities && sh && viewmats && Ks && campos && splats && v_splats && grads);
-    return st3r_project_sh_bwd_impl((hipStream_t)stream, GsParams{N, means, quats, scales, opacities, sh, sh_stride},
+    GsParams g{N, means, quats, scales, opacities, sh, sh_stride};
+    const int rc = st3r_sh_setting(ctx, &g, true);
+    if (rc) return rc;
+    return st3r_project_sh_bwd_impl((hipStream_t)stream, g,
                                     GsViews{C, width, height, viewmats, Ks, campos}, eps2d, splats, v_splats, reg_views, opac_fac, scale_fac,
                                     grads, false, 0, -1, false, nullptr);
 }

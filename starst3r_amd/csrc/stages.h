@@ -10,7 +10,25 @@ struct GsParams {   // the Gaussians: [N,3] [N,4] [N,3] [N] [N,sh_stride]
     int N;
     const float *means, *quats, *scales, *opacities, *sh;
     int sh_stride;
+    // the SH setting of the call (st3r_sh_setting fills it from the context): SH_ROWS(sh_active) rows are evaluated, the
+    // gradients of the rows 4 .. SH_ROWS(sh_degree) - 1 go to v_sh_high [N, 3 (SH_ROWS(sh_degree) - 4)]
+    int sh_active = 1, sh_degree = 1;
+    float* v_sh_high = nullptr;
 };
+
+// The context's SH setting (st3r_ctx_set_sh_degree) onto the Gaussians of a call that evaluates SH, with the two checks
+// every such call makes: the rows are there, and a backward call at degree >= 2 has somewhere to write.
+static inline int st3r_sh_setting(const st3r_ctx* ctx, GsParams* g, bool backward) {
+    const int rows = (ctx->sh_degree + 1) * (ctx->sh_degree + 1);
+    ARG_CHECK(g->sh_stride >= 3 * (rows < 4 ? 4 : rows));
+    if (backward && ctx->sh_degree >= 2 && !ctx->sh_v_high) {
+        st3r_set_error("the SH degree is %d and no v_sh_high is set -- a backward call needs it "
+                       "(st3r_ctx_set_sh_degree(ctx, degree, active_degree, v_sh_high))", ctx->sh_degree);
+        return ST3R_ERR_INVALID;
+    }
+    g->sh_active = ctx->sh_active; g->sh_degree = ctx->sh_degree; g->v_sh_high = ctx->sh_v_high;
+    return ST3R_OK;
+}
 
 struct GsViews {   // C views of W x H pixels: [C,4,4] [C,3,3] [C,3]
     int C, W, H;

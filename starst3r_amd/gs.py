@@ -82,6 +82,10 @@ class _OptimState:
             off += w
         self.m, self.v, self.N = m, v, n_total
         self.grads = torch.empty(23 * n_total, device=m.device)
+        if getattr(self, "sh_m", None) is not None:   # scene.sh_degree 2 or 3: the high SH rows' block grows with it
+            pad = torch.zeros((n_total - self.sh_m.shape[0], self.sh_m.shape[1]), device=m.device)
+            self.sh_m, self.sh_v = torch.cat([self.sh_m, pad]), torch.cat([self.sh_v, pad])
+            self.sh_grad = torch.zeros_like(self.sh_m)
 
     def block_slice(self, key):
         off = 0
@@ -147,6 +151,12 @@ class MCMCStrategy:
         P = {k: params[k].data for k in GAUSSIAN_KEYS}
         state["n_relocated"] = ops.mcmc_relocate(ctx, P, owner.m, owner.v, self.min_opacity, seed, call)
         N = P["means"].shape[0]
+        if getattr(owner, "sh_m", None) is not None and owner.sh_m.shape[0] == N:
+            # scene.sh_degree 2 or 3: the moments of the high SH rows restart where the relocation restarted the others --
+            # on the Gaussians it drew as sources (the draw counts the context keeps, st3r_ctx_peek 7)
+            src = ops.peek(ctx, 7, N, torch.int32) > 0
+            owner.sh_m[src] = 0.0
+            owner.sh_v[src] = 0.0
         n_new = max(0, min(self.cap_max, int(1.05 * N)) - N)
         if n_new > 0:
             grown = {}
@@ -179,12 +189,40 @@ def _activations(scene):
     return on
 
 
+def _sh_degree(scene):
+    """scene.sh_degree (absent or None: nothing about any call changes): the SH degree the scene's colours are evaluated at,
+    an int 0..3; ValueError for a bool or anything else"""
+    d = getattr(scene, "sh_degree", None)
+    if d is None:
+        return None
+    if isinstance(d, bool) or not isinstance(d, (int, np.integer)) or not 0 <= int(d) <= 3:
+        raise ValueError(f"scene.sh_degree is None or an int 0..3, got {d!r}")
+    return int(d)
+
+
+@contextlib.contextmanager
+def _sh_setting(ctx, degree, active=None, v_sh_high=None):
+    """the ctx evaluates SH at `degree` (ops.set_sh_degree) inside the block and at what it had before behind it; None:
+    nothing is set"""
+    if degree is None:
+        yield
+        return
+    prev = ops.set_sh_degree(ctx, degree, active, v_sh_high)
+    try:
+        yield
+    finally:
+        ops.set_sh_degree(ctx, *prev)
+
+
 def init_3dgs(scene, init_scale=3e-3, lr=1e-3):
     """Initialize 3DGS splats and optims from Mast3r dense points (reference gs.py:14-45).
 
     With scene.activations = True (not in the reference) the scales are log(init_scale) and the opacities
     logit(scene.init_opacity) -- init_opacity a setting of the scene, default 0.1 as in gsplat's trainer; an init_scale
-    <= 0 or an init_opacity outside (0, 1) raises ValueError before anything is allocated.  Everything else is as without."""
+    <= 0 or an init_opacity outside (0, 1) raises ValueError before anything is allocated.  Everything else is as without.
+    With scene.sh_degree set to an int (not in the reference) sh0 and row 0 of shN are (colour - 0.5) / C0 and rows 1..23 are
+    zero -- the canonical initialisation; the reference fills all 24 rows with 1 - colour, which at degree 3 would start
+    training from strong spurious view dependence.  With the setting absent or None the tensors are the reference's."""
     scale_0, opacity_0 = init_scale, 1.0
     if _activations(scene):
         p = getattr(scene, "init_opacity", 0.1)
@@ -208,9 +246,14 @@ def init_3dgs(scene, init_scale=3e-3, lr=1e-3):
         "shN": torch.zeros(n, 24, 3),
     }
     g["quats"][:, 0] = 1.0
-    inv = (1 - colors).float()
-    g["sh0"][:, 0] = inv
-    g["shN"][:] = inv[:, None, :]
+    if _sh_degree(scene) is None:
+        inv = (1 - colors).float()
+        g["sh0"][:, 0] = inv
+        g["shN"][:] = inv[:, None, :]
+    else:   # canonical: the DC term alone carries the colour, C0 k0 + 0.5 = colour; no spurious view dependence
+        dc = (colors.float() - 0.5) / 0.2820947917738781
+        g["sh0"][:, 0] = dc
+        g["shN"][:, 0] = dc
     scene.gaussians = {k: torch.nn.Parameter(v.to(scene.device).contiguous(), requires_grad=True) for k, v in g.items()}
     scene._gs_optim = _OptimState(scene, lr)
     scene.optimizers = {k: FusedAdam(scene._gs_optim, k) for k in scene.gaussians}
@@ -273,10 +316,12 @@ class _Rasterize(torch.autograd.Function):
     through project_sh_bwd / viewmat_bwd once; the depth column (z of the record) is added by st3r_gs_depth_bwd."""
 
     @staticmethod
-    def forward(fctx, means, quats, scales, opacities, shN, w2c, Ks, width, height, ctx, want_depth, want_Ks=False):
-        rgb, alpha, info = ops.rasterization(ctx, means, quats, scales, opacities, shN, w2c, Ks, width, height)
+    def forward(fctx, means, quats, scales, opacities, shN, w2c, Ks, width, height, ctx, want_depth, want_Ks=False,
+                sh_degree=None):
+        with _sh_setting(ctx, sh_degree):
+            rgb, alpha, info = ops.rasterization(ctx, means, quats, scales, opacities, shN, w2c, Ks, width, height)
         fctx.save_for_backward(means, quats, scales, opacities, shN, w2c, Ks, alpha)
-        fctx.info, fctx.ctx, fctx.wh, fctx.want_Ks = info, ctx, (width, height), want_Ks
+        fctx.info, fctx.ctx, fctx.wh, fctx.want_Ks, fctx.sh_degree = info, ctx, (width, height), want_Ks, sh_degree
         if not want_depth:
             return rgb, alpha
         fctx.set_materialize_grads(False)   # an output the loss does not use costs no backward kernel
@@ -304,14 +349,19 @@ class _Rasterize(torch.autograd.Function):
             v_splats = v_d if v_splats is None else v_splats.add_(v_d)   # (disjoint: colour floats 6-8, depth float 9)
         if v_splats is None:
             v_splats = torch.zeros_like(info["_splats"])
-        grads = ops.project_sh_bwd(ctx, means, quats, scales, opacities, shN, w2c, Ks, info["_campos"], W, H,
-                                   info["_splats"], v_splats)
+        # scene.sh_degree: the two kernels that evaluate SH run at the degree of the forward; the rows 4.. of v_shN
+        deg, v_hi = fctx.sh_degree, None
+        if deg is not None and deg >= 2:
+            v_hi = torch.empty((N, 3 * (ops.sh_rows(deg) - 4)), dtype=torch.float32, device=means.device)
         # camera poses: only when asked for (gsplat's v_viewmats); intrinsics: only with scene.intrinsics_grad
         # (gsplat returns none) -- the depth column of v_splats does not depend on K
         v_w2c = v_Ks = None
-        if fctx.needs_input_grad[5]:
-            v_w2c = ops.viewmat_bwd(ctx, means, quats, scales, shN, w2c, Ks, info["_campos"], W, H, info["_splats"],
-                                    v_splats)
+        with _sh_setting(ctx, deg, deg, v_hi):
+            grads = ops.project_sh_bwd(ctx, means, quats, scales, opacities, shN, w2c, Ks, info["_campos"], W, H,
+                                       info["_splats"], v_splats)
+            if fctx.needs_input_grad[5]:
+                v_w2c = ops.viewmat_bwd(ctx, means, quats, scales, shN, w2c, Ks, info["_campos"], W, H, info["_splats"],
+                                        v_splats)
         if fctx.want_Ks and fctx.needs_input_grad[6]:
             v4 = ops.intrinsics_bwd(ctx, means, quats, scales, w2c, Ks, W, H, info["_splats"], v_splats)
             v_Ks = torch.zeros_like(Ks)
@@ -321,7 +371,9 @@ class _Rasterize(torch.autograd.Function):
         G = ops.split_grads(grads, N)
         v_sh = torch.zeros_like(shN)
         v_sh[:, :4] = G["sh"]
-        return G["means"], G["quats"], G["scales"], G["opacities"], v_sh, v_w2c, v_Ks, None, None, None, None, None
+        if v_hi is not None:
+            v_sh[:, 4:ops.sh_rows(deg)] = v_hi.view(N, -1, 3)
+        return G["means"], G["quats"], G["scales"], G["opacities"], v_sh, v_w2c, v_Ks, None, None, None, None, None, None
 
 
 class _Exposure(torch.autograd.Function):
@@ -412,10 +464,16 @@ def render_3dgs(scene, w2c: torch.Tensor, intrinsics: torch.Tensor, width: int, 
     scene.activations (not in the reference; a setting of the scene, default False; anything but a bool raises ValueError):
     True reads scene.gaussians["scales"] as log-scales and ["opacities"] as logits -- the render sees exp and sigmoid of
     them (st3r_param_activate) in every render_mode and with every option above, back-propagates into the logs and logits,
-    and info["opacities"] holds the activated values, as in gsplat."""
+    and info["opacities"] holds the activated values, as in gsplat.
+    scene.sh_degree (not in the reference, which evaluates degree 1 on rows 0..3 of shN; a setting of the scene; absent or
+    None: exactly that; a bool or anything but an int 0..3 raises ValueError): the colours are evaluated at this degree, on
+    rows 0 .. (sh_degree + 1)^2 - 1 of shN (st3r_ctx_set_sh_degree, set around the call and restored behind it), in every
+    render_mode and with every option above; the backward pass fills those rows of shN.grad and takes the pose gradient
+    through the same degree."""
     if render_mode not in RENDER_MODES:
         raise ValueError(f"render_mode must be one of {RENDER_MODES}, got {render_mode!r}")
     activated = _activations(scene)
+    sh_degree = _sh_degree(scene)
     backgrounds = _render_backgrounds(scene, w2c.shape[0], render_mode)
     if exposure is not None:
         _check_render_exposure(exposure, w2c.shape[0], render_mode)
@@ -428,7 +486,7 @@ def render_3dgs(scene, w2c: torch.Tensor, intrinsics: torch.Tensor, width: int, 
         backgrounds = backgrounds.to(scene.device, torch.float32)
     scales, opacities = _Activate.apply(g["scales"], g["opacities"], ctx) if activated else (g["scales"], g["opacities"])
     out = _Rasterize.apply(g["means"], g["quats"], scales, opacities, g["shN"], w2c, Ks, width, height, ctx,
-                           render_mode != "RGB", bool(getattr(scene, "intrinsics_grad", False)))
+                           render_mode != "RGB", bool(getattr(scene, "intrinsics_grad", False)), sh_degree)
     if render_mode == "RGB":
         rgb, alpha = out
         if backgrounds is not None:
@@ -932,6 +990,73 @@ class _Activations(_PerViewOption):
         ops.set_activation(c.ctx, False)
 
 
+def _sh_active_degree(t, interval, degree):
+    """the degree the step with 1-based Adam counter t evaluates: one more band every `interval` steps (gsplat's trainer),
+    the full degree from the first step with interval 0"""
+    return degree if interval <= 0 else min((t - 1) // interval, degree)
+
+
+class _ShDegree(_PerViewOption):
+    """scene.sh_degree: the ctx evaluates SH at the scene's degree -- at the schedule's active degree, step by step -- for
+    the duration of the call, and the rows 4.. of shN are trained by an Adam step of their own behind the training step.
+    Its gradient buffer and moments live on scene._gs_optim (sh_grad, sh_m, sh_v [N, 3 (rows - 4)], sh_step)."""
+    spelled, schedule, counter = "scene.sh_degree", False, "sh_step"
+
+    @classmethod
+    def when_on(cls, scene, enable_pruning):
+        degree = _sh_degree(scene)
+        if degree is None:
+            return None
+        interval = getattr(scene, "sh_degree_interval", 0)
+        if isinstance(interval, bool) or not isinstance(interval, (int, np.integer)) or interval < 0:
+            raise ValueError(f"scene.sh_degree_interval is an int >= 0, got {interval!r}")
+        rate = getattr(scene, "sh_high_lr", None)
+        if rate is not None and (isinstance(rate, bool) or not isinstance(rate, (int, float, np.floating, np.integer))
+                                 or not float(rate) >= 0.0):
+            raise ValueError(f"scene.sh_high_lr is None or a float >= 0, got {rate!r}")
+        _single_replica_only(cls.spelled, scene, enable_pruning)
+        if enable_pruning and degree >= 2 and type(getattr(scene, "strategy", None)) is not MCMCStrategy:
+            raise NotImplementedError("scene.sh_degree >= 2 together with enable_pruning needs the project's own "
+                                      "MCMCStrategy: another strategy object does not carry the moments of the SH rows 4..")
+        return cls(degree, int(interval), rate)
+
+    def __init__(self, degree, interval, rate):
+        self.degree, self.interval, self.rate = degree, interval, rate
+        self.rows = max(ops.sh_rows(degree), 4)   # rows of the compact SH copy the loop trains
+
+    def set_up(self, c):
+        st, n = c.st, c.scene.gaussians["means"].shape[0]
+        if not hasattr(st, "sh_step"):
+            st.sh_step = 0
+        if self.degree < 2:
+            return
+        width = 3 * (self.rows - 4)
+        m = getattr(st, "sh_m", None)
+        if m is None or m.shape[1] != width:          # first use, or another degree: a new parameter block
+            st.sh_m = torch.zeros((0, width), device=c.scene.device); st.sh_v = torch.zeros_like(st.sh_m)
+            st.sh_step = 0
+        if st.sh_m.shape[0] != n:                     # the set grew: the new Gaussians start from zero moments
+            grow = lambda t: torch.cat([t[:n], torch.zeros((max(n - t.shape[0], 0), width), device=t.device)])
+            st.sh_m, st.sh_v = grow(st.sh_m), grow(st.sh_v)
+        st.sh_grad = torch.zeros((n, width), device=c.scene.device)
+
+    def before_step(self, c, sh):
+        """the setting of this step: its active degree by the Gaussians' Adam counter"""
+        self.active = _sh_active_degree(c.st.step, self.interval, self.degree)
+        self.sh = sh
+        ops.set_sh_degree(c.ctx, self.degree, self.active, c.st.sh_grad if self.degree >= 2 else None)
+
+    def clear(self, c):
+        ops.set_sh_degree(c.ctx, *ops.SH_DEFAULT)
+
+    def behind_step(self, c, step):
+        if self.degree >= 2:
+            st = c.st
+            ops.sh_high_adam_step(c.ctx, self.sh, self.degree, st.sh_grad, st.sh_m, st.sh_v,
+                                  st.lr if self.rate is None else float(self.rate), st.betas[0], st.betas[1], st.eps,
+                                  st.sh_step)
+
+
 def _iterations(iters, verbose):
     """range(iters), with a progress bar when verbose"""
     if verbose:
@@ -1064,8 +1189,22 @@ def run_3dgs_optim(
     Adam, the moments and their layout do not change.  init_3dgs under the setting, or activate_3dgs on a raw scene, produce
     such tensors.  Works together with every option above and enable_pruning; single process, Gaussians replicated only.
     With the setting off nothing about the call changes.
+    scene.sh_degree (not in the reference, which trains degree 1 on rows 0..3 of shN; a setting of the scene; absent or
+    None: exactly that, and nothing is set on the context; a bool or anything but an int 0..3 raises ValueError): the fused
+    step evaluates the colours at this degree, the compact SH copy holds (sh_degree + 1)^2 rows (at least 4), and the rows
+    4.. are trained by an Adam step of their own behind every training step (st3r_sh_high_adam_step, guarded on the device
+    like the Gaussians': the capacity-overflow repeat needs nothing new) at scene.sh_high_lr (None: the Gaussians' rate).
+    scene.sh_degree_interval (default 0: the full degree from the first step): n > 0 evaluates, at the step with 1-based
+    Adam counter t, the degree min((t - 1) // n, sh_degree) -- gsplat's trainer schedule.  The high rows' gradient and
+    moments persist on scene._gs_optim (sh_grad, sh_m, sh_v, sh_step) from call to call.  Works together with every option
+    above and with enable_pruning under the project's own MCMCStrategy -- relocation and growth copy whole shN rows, a
+    refinement step zeroes the rows of sh_m / sh_v of the Gaussians the relocation drew as sources, and sh_grad, sh_m and
+    sh_v grow with zeros when the set grows; another strategy object together with sh_degree >= 2 raises
+    NotImplementedError --; single process, Gaussians replicated only.  init_3dgs under the setting starts from the
+    canonical DC-only colours.
     """
     activations = _Activations.when_on(scene, enable_pruning)   # (its check comes first)
+    sh_degree = _ShDegree.when_on(scene, enable_pruning)
     masks = _LossMasks.when_on(scene, enable_pruning, getattr(scene, "loss_masks", None))   # (its checks come first)
     backgrounds = _Backgrounds.when_on(scene, enable_pruning, getattr(scene, "backgrounds", None))
     alphas = _AlphaMasks.when_on(scene, enable_pruning, getattr(scene, "alpha_fac", 0.0), getattr(scene, "alpha_masks", None),
@@ -1075,7 +1214,8 @@ def run_3dgs_optim(
     exposures = _Exposures.when_on(scene, enable_pruning, exposure_lr, exposure_freeze)
     intrinsics = _Intrinsics.when_on(scene, enable_pruning, getattr(scene, "intrinsics_lr", 0.0))
     # in this order at every hook: checks (above), set-up, registration, clearing, behind the step, finish
-    options = [o for o in (depth, poses, exposures, intrinsics, masks, backgrounds, alphas, activations) if o is not None]
+    options = [o for o in (depth, poses, exposures, intrinsics, masks, backgrounds, alphas, activations, sh_degree)
+               if o is not None]
     counters = [o.counter for o in options if o.counter]
     height, width = scene.imgs[0].shape[:2]
     ctx = ops.get_context(scene.device)
@@ -1108,16 +1248,20 @@ def run_3dgs_optim(
     # trains a COMPACT copy [N, 4, 3] (sh_stride = 12) and writes it back into rows 0..3 of `shN` when it ends, and before
     # every strategy hook that may look at the parameters (measured at 1 M Gaussians: projection 0.183 -> 0.157 ms, its
     # backward 0.223 -> 0.203, Adam 0.148 -> 0.105; tools/experiments/ab_compact_sh.sh).
-    sh_c = [g["shN"].data[:, :4].contiguous()]
+    # (scene.sh_degree 2 or 3: the 9 or 16 rows in use)
+    sh_rows = 4 if sh_degree is None else sh_degree.rows
+    sh_c = [g["shN"].data[:, :sh_rows].contiguous()]
 
     def sh_write_back():
-        g["shN"].data[:, :4].copy_(sh_c[0])
+        g["shN"].data[:, :sh_rows].copy_(sh_c[0])
 
     def one_iteration(step):
         if sh_c[0].shape[0] != g["shN"].shape[0]:   # the set grew (a refinement step replaced the tensors)
-            sh_c[0] = g["shN"].data[:, :4].contiguous()
+            sh_c[0] = g["shN"].data[:, :sh_rows].contiguous()
         P = {k: g[k].data for k in ("means", "quats", "scales", "opacities")}  # growth replaces the tensors
         P["shN"] = sh_c[0]
+        if sh_degree is not None:
+            sh_degree.before_step(c, sh_c[0])
         # which step call: the one branch on a specific option, because that is how the C interface is shaped
         if poses is not None:   # the same single call, and the cameras move in it too (w2c and campos in place)
             ops.train_step_poses(ctx, P, w2c, Ks, campos, gt, width, height, loss_ssim_fac, loss_opacity_fac,
@@ -1159,7 +1303,7 @@ def run_3dgs_optim(
                         sh_write_back()
                     scene.strategy.step_pre_backward(g, scene.optimizers, scene.strategy_state, step, None)
                     if not own_strategy:
-                        sh_c[0] = g["shN"].data[:, :4].contiguous()
+                        sh_c[0] = g["shN"].data[:, :sh_rows].contiguous()
                 count_step(1)
                 try:
                     one_iteration(step)
@@ -1187,7 +1331,7 @@ def run_3dgs_optim(
                         sh_write_back()
                     scene.strategy.step_post_backward(g, scene.optimizers, scene.strategy_state, step, None, 1e-3)
                     if touch:
-                        sh_c[0] = g["shN"].data[:, :4].contiguous()
+                        sh_c[0] = g["shN"].data[:, :sh_rows].contiguous()
                 step += 1
             if world == 1 and iters > 0:
                 try:   # the last step's count is still in flight: settle it now so that an overflow cannot go unnoticed

@@ -5,6 +5,7 @@ raw device pointers to libst3r_hip.so.  All tensors must live on the context's G
 """
 import ctypes as C
 import math
+import numbers
 
 import torch
 
@@ -527,6 +528,64 @@ def get_activation(ctx):
     on = C.c_int(-1)
     _lib.check(_lib.lib().st3r_ctx_get_activation(ctx.handle, C.byref(on)))
     return bool(on.value)
+
+
+SH_DEFAULT = (1, 1, None)
+
+
+def sh_rows(degree):
+    """rows of an SH tensor of this degree"""
+    return (degree + 1) ** 2
+
+
+def set_sh_degree(ctx, degree, active_degree=None, v_sh_high=None):
+    """The SH degree every call that evaluates SH uses from now on (a setting of the ctx, st3r_ctx_set_sh_degree):
+    project_sh, project_sh_bwd, viewmat_bwd, render and the training calls read sh_rows(active_degree) rows of `sh`; the
+    backward calls leave the gradients of the rows 4.. in v_sh_high [N, 3 (sh_rows(degree) - 4)] (needed by them for
+    degree >= 2, kept alive here).  active_degree None: degree.  Returns the previous setting, a tuple that
+    set_sh_degree(ctx, *prev) restores; a ctx starts at SH_DEFAULT."""
+    if isinstance(degree, bool) or not isinstance(degree, numbers.Integral) or not 0 <= degree <= 3:
+        raise ValueError(f"sh degree must be an int 0..3, got {degree!r}")
+    active = degree if active_degree is None else active_degree
+    if isinstance(active, bool) or not isinstance(active, numbers.Integral) or not 0 <= active <= degree:
+        raise ValueError(f"active sh degree must be an int 0..{degree}, got {active!r}")
+    degree, active = int(degree), int(active)
+    address = isinstance(v_sh_high, int)   # (what get_sh_degree returns for a buffer set behind this module's back)
+    if v_sh_high is not None and not address:
+        if degree < 2:
+            raise ValueError("v_sh_high belongs to sh degree 2 or 3")
+        if v_sh_high.dim() != 2 or v_sh_high.shape[1] != 3 * (sh_rows(degree) - 4):
+            raise ValueError(f"v_sh_high must be [N, {3 * (sh_rows(degree) - 4)}], got {tuple(v_sh_high.shape)}")
+    prev = get_sh_degree(ctx)
+    _lib.check(_lib.lib().st3r_ctx_set_sh_degree(ctx.handle, degree, active,
+                                                 C.c_void_p(v_sh_high) if address else _p(v_sh_high)))
+    ctx._sh_keep = None if address else v_sh_high
+    return prev
+
+
+def get_sh_degree(ctx):
+    """(degree, active_degree, v_sh_high) of the ctx (st3r_ctx_get_sh_degree).  v_sh_high is the tensor set_sh_degree keeps
+    alive when the context still points at it, None for a NULL pointer, and the bare address (an int) of a buffer that
+    was set behind this module's back."""
+    if not hasattr(ctx, "handle"):       # a stand-in without a library context: the default, as a context starts
+        return SH_DEFAULT
+    d, a, p = C.c_int(-1), C.c_int(-1), C.c_void_p()
+    _lib.check(_lib.lib().st3r_ctx_get_sh_degree(ctx.handle, C.byref(d), C.byref(a), C.byref(p)))
+    kept = getattr(ctx, "_sh_keep", None)
+    if not p.value:
+        v = None
+    else:
+        v = kept if kept is not None and kept.data_ptr() == p.value else int(p.value)
+    return d.value, a.value, v
+
+
+def sh_high_adam_step(ctx, sh, degree, v_sh_high, m, v, lr, b1, b2, eps, step):
+    """One Adam step on the rows 4 .. sh_rows(degree) - 1 of sh [N, rows, 3], in place, from v_sh_high; moments m, v
+    [N, 3 (sh_rows(degree) - 4)] (st3r_sh_high_adam_step).  Guarded on the device like adam_step."""
+    N, H = sh.shape[0], 3 * (sh_rows(degree) - 4)
+    assert degree in (2, 3) and all(tuple(t.shape) == (N, H) for t in (v_sh_high, m, v))
+    _lib.check(_lib.lib().st3r_sh_high_adam_step(ctx.handle, _stream(), N, _p(sh), sh_stride_of(sh), degree,
+                                                 _p(v_sh_high), _p(m), _p(v), lr, b1, b2, eps, step))
 
 
 def intrinsics_adam_step(ctx, Ks, v_Ks, k_m, k_v, lr, b1, b2, eps, step, mask, W, H, tie_focal=True, opt_pp=False):
