@@ -150,6 +150,23 @@ static inline int view_reg_set(ViewReg* r, bool on, const float* gt, int C, int 
     return ST3R_OK;
 }
 
+// A weighted per-pixel target registered for a set of views -- the depth prior and the alpha targets are two of these:
+// the target and weight maps [c,h,w] (caller-owned), the factor of its loss term (0: none), and norm_valid: the option's
+// norm slot holds the n_c = max(sum w_c, 1) of this registration (computed by the first training call that uses it).
+struct TargetReg { ViewReg reg; const float* map; const float* weight; float fac; int norm_valid; };
+
+// st3r_ctx_set_depth_prior / st3r_ctx_set_alpha_target; fac_ok: the setter's own check of its factor
+static inline int target_reg_set(TargetReg* r, const float* gt, const float* map, const float* weight, int C, int height,
+                                 int width, float fac, bool fac_ok) {
+    r->norm_valid = 0;
+    const bool on = gt && map && weight;
+    ARG_CHECK(!on || fac_ok);
+    int rc = view_reg_set(&r->reg, on, gt, C, height, width);
+    if (rc) return rc;
+    r->map = on ? map : nullptr; r->weight = on ? weight : nullptr; r->fac = on ? fac : 0.f;
+    return ST3R_OK;
+}
+
 struct st3r_ctx {
     int device;
     void* slot_ptr[SLOT_COUNT];
@@ -168,9 +185,9 @@ struct st3r_ctx {
     // What the caller registered for a set of views (ViewReg) and each option's payload: caller-owned, valid until cleared.
     // ground-truth moments (st3r_ctx_set_gt_moments, loss.hip)
     ViewReg gtm; const float* gtm_mom;
-    // depth prior (st3r_ctx_set_depth_prior, loss_depth.hip); dp_fac == 0: none; dp_norm_valid: SLOT_DPRIOR_NORM holds
-    // the n_c of this registration (computed by the first training call that uses it)
-    ViewReg dp; const float* dp_depth; const float* dp_weight; float dp_fac; int dp_norm_valid;
+    // depth prior (st3r_ctx_set_depth_prior, loss_depth.hip) and alpha targets (st3r_ctx_set_alpha_target, gs_alpha.hip);
+    // their norms live in SLOT_DPRIOR_NORM and SLOT_ATARGET_NORM
+    TargetReg dp, at;
     // exposures (st3r_ctx_set_exposure, gs_exposure.hip)
     ViewReg ex; const float* ex_exposure; float* ex_v_exposure;
     // intrinsics gradient (st3r_ctx_set_intrinsics_grad, gs_intrinsics.hip): where d loss / d (fx, fy, cx, cy) goes
@@ -180,9 +197,6 @@ struct st3r_ctx {
     ViewReg lw; const float* lw_weight; int lw_norm_valid;
     // backgrounds (st3r_ctx_set_background, gs_alpha.hip): [c,3]
     ViewReg bg; const float* bg_colors;
-    // alpha targets (st3r_ctx_set_alpha_target, gs_alpha.hip); at_fac == 0: none; at_norm_valid: SLOT_ATARGET_NORM holds
-    // the n_c of this registration (computed by the first training call that uses it)
-    ViewReg at; const float* at_target; const float* at_weight; float at_fac; int at_norm_valid;
     // activated parameters (st3r_ctx_set_activation, gs_activation.hip): the fused steps and st3r_gs_render read the scales
     // as logs and the opacities as logits
     int activation;

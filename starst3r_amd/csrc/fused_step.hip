@@ -218,12 +218,13 @@ static int rasterize_front(st3r_ctx* ctx, hipStream_t s, const GsParams& g, cons
     return ST3R_OK;
 }
 
+// one weighted-target term of the loss (depth prior, alpha targets): fac sum_c sums[c] / norm[c]; sums == NULL: none
+struct TargetTerm { const double* sums; const double* norm; double fac; };
+
 __global__ void k_finalize_loss(int C, const double* __restrict__ sums, const double* __restrict__ reg_sums,
                                 double inv_px, double inv_cnt, double w_l1, double w_ssim, double reg_views,
                                 double opac_k, double scale_k, float* __restrict__ loss_out,
-                                const double* __restrict__ dsums, const double* __restrict__ dnorm, double depth_fac,
-                                const double* __restrict__ wnorm, const double* __restrict__ asums,
-                                const double* __restrict__ anorm, double alpha_fac) {
+                                const double* __restrict__ wnorm, TargetTerm depth, TargetTerm alpha) {
     if (threadIdx.x == 0 && blockIdx.x == 0) {
         double loss = 0;
         if (wnorm)   // per-pixel weights (loss.hip): wnorm[2c], wnorm[2c + 1] = sum_p w, sum_{p in I} w of view c
@@ -233,48 +234,41 @@ __global__ void k_finalize_loss(int C, const double* __restrict__ sums, const do
         else
             for (int c = 0; c < C; ++c) loss += w_l1 * sums[2 * c] * inv_px + w_ssim * (1.0 - sums[2 * c + 1] * inv_cnt);
         loss += reg_views * (opac_k * reg_sums[0] + scale_k * reg_sums[1]);
-        if (dsums)   // depth prior (loss_depth.hip): depth_fac sum_p w |ED - Z| / n_c per view
-            for (int c = 0; c < C; ++c) loss += depth_fac * dsums[c] / dnorm[c];
-        if (asums)   // alpha targets (gs_alpha.hip): alpha_fac sum_p w |a - M| / n_c per view
-            for (int c = 0; c < C; ++c) loss += alpha_fac * asums[c] / anorm[c];
+        if (depth.sums)   // depth prior (loss_depth.hip): depth_fac sum_p w |ED - Z| / n_c per view
+            for (int c = 0; c < C; ++c) loss += depth.fac * depth.sums[c] / depth.norm[c];
+        if (alpha.sums)   // alpha targets (gs_alpha.hip): alpha_fac sum_p w |a - M| / n_c per view
+            for (int c = 0; c < C; ++c) loss += alpha.fac * alpha.sums[c] / alpha.norm[c];
         loss_out[0] = (float)loss;
     }
 }
 
-// the per-view sums of a step -> its loss; dp_sums == NULL: no depth term; lw.weight != NULL: the weighted loss, normalised
-// by the sums of the views' weights; at_sums == NULL: no alpha term
+// the per-view sums of a step -> its loss; o: the depth and alpha terms, and the weighted loss, normalised by the sums of
+// the views' weights
 static int finalize_loss(hipStream_t s, int C, int H, int W, const double* sums, const double* reg_sums, float ssim_fac,
-                         double reg_views, double opac_k, double scale_k, float* loss_out, const double* dp_sums,
-                         const DepthPrior& dp, const LossWeight& lw, const double* at_sums = nullptr,
-                         const AlphaTarget& at = AlphaTarget{}) {
+                         double reg_views, double opac_k, double scale_k, float* loss_out, const StepOptions& o) {
     const int Hi = H - 10, Wi = W - 10;
     const double cnt = (Hi > 0 && Wi > 0) ? (double)Hi * Wi * 3 : 0.0;
     hipLaunchKernelGGL(k_finalize_loss, dim3(1), dim3(64), 0, s, C, sums, reg_sums, 1.0 / ((double)H * W * 3),
                        cnt > 0 ? 1.0 / cnt : 0.0, (double)(1.0f - ssim_fac), (double)ssim_fac, reg_views, opac_k, scale_k,
-                       loss_out, dp_sums, dp.norm, (double)dp.fac, lw.weight ? lw.norm : nullptr, at_sums, at.norm,
-                       (double)at.fac);
+                       loss_out, o.lw.norm, TargetTerm{o.dp_sums, o.dp.norm, (double)o.dp.fac},
+                       TargetTerm{o.at_sums, o.at.norm, (double)o.at.fac});
     LAUNCH_CHECK();
     return ST3R_OK;
 }
 
 struct LossFacs { float ssim, opac, scale; };
 
-// A set of views with what a training call compares them against and where their per-view results go: the whole call,
-// or one view chunk of it.  dp_sums / v_viewmats may be NULL (no depth prior / no pose gradient wanted).
+// A set of views with what a training call compares them against, what is registered for them and where their per-view
+// results go: the whole call, or one view chunk of it.  v_viewmats may be NULL (no pose gradient wanted).
 struct ViewBatch {
     GsViews v;
     const float* gt;      // [C,H,W,3]
     double* sums;         // [C,2]: L1 and SSIM sums
-    double* dp_sums;      // [C]: sum_p w |ED - Z|
     float* v_viewmats;    // [C,4,4]
-    bool exposure;        // exposures may be registered for these views (st3r_ctx_set_exposure)
-    bool weighted;        // per-pixel loss weights may be registered for these views (st3r_ctx_set_loss_weight)
-    bool background;      // backgrounds may be registered for these views (st3r_ctx_set_background)
-    double* at_sums;      // [C]: sum_p w |a - M| (st3r_ctx_set_alpha_target); NULL: no alpha targets
+    StepOptions opt;
     ViewBatch slice(int c0, int c1) const {
-        return {v.slice(c0, c1), gt + (int64_t)c0 * v.H * v.W * 3, sums + 2 * c0, dp_sums ? dp_sums + c0 : nullptr,
-                v_viewmats ? v_viewmats + 16 * c0 : nullptr, exposure, weighted, background,
-                at_sums ? at_sums + c0 : nullptr};
+        return {v.slice(c0, c1), gt + (int64_t)c0 * v.H * v.W * 3, sums + 2 * c0,
+                v_viewmats ? v_viewmats + 16 * c0 : nullptr, opt.slice(c0, (int64_t)v.H * v.W)};
     }
 };
 
@@ -282,43 +276,45 @@ struct ViewBatch {
 // or alpha targets; exposed: with exposures only; composite: with backgrounds only)
 struct StepImages { float *rgb, *alpha; int32_t* last; float *v_rgb, *depth, *v_depth, *v_alpha, *exposed, *composite; };
 
-static int step_images(st3r_ctx* ctx, const RasterOut& ro, bool with_depth, bool with_exposure, bool with_background,
-                       bool with_v_alpha, StepImages* im) {
+static int step_images(st3r_ctx* ctx, const RasterOut& ro, const StepOptions& o, StepImages* im) {
     const int64_t n_px = (int64_t)ro.C * ro.H * ro.W;
     ARENA_GET(SLOT_RGB, float, n_px * 3, rgb);
     ARENA_GET(SLOT_ALPHA, float, n_px, alpha);
     ARENA_GET(SLOT_LAST, int32_t, n_px, last);
     ARENA_GET(SLOT_VRENDER, float, n_px * 3, v_rgb);
     *im = StepImages{rgb, alpha, last, v_rgb, nullptr, nullptr, nullptr, nullptr, nullptr};
-    if (with_exposure) {
+    if (o.ex.exposure) {
         ARENA_GET(SLOT_EXPOSED, float, n_px * 3, exposed);
         im->exposed = exposed;
     }
-    if (with_background) {
+    if (o.bg.colors) {
         ARENA_GET(SLOT_COMPOSITE, float, n_px * 3, composite);
         im->composite = composite;
     }
-    if (with_depth) {
+    if (o.dp.map) {
         ARENA_GET(SLOT_DEPTH, float, n_px, depth);
         ARENA_GET(SLOT_VDEPTH, float, n_px, v_depth);
         im->depth = depth; im->v_depth = v_depth;
     }
-    if (with_depth || with_v_alpha) {
+    if (o.dp.map || o.bg.colors || o.at.map) {
         ARENA_GET(SLOT_VALPHA, float, n_px, v_alpha);
         im->v_alpha = v_alpha;
     }
     return ST3R_OK;
 }
 
-// Blend forward and the losses of the views in b: their sums go to b.sums (and b.dp_sums), d loss / d image to im.
-// dp.prior != NULL: the step also renders the depth map of the same lists and takes the prior's loss, which sends v_D
-// and v_alpha back.
+// Blend forward and the losses of the views in b: their sums go to b.sums (and b.opt.dp_sums, b.opt.at_sums), d loss /
+// d image to im.  Of b.opt:
 static int forward_and_losses(st3r_ctx* ctx, hipStream_t s, const RasterOut& ro, const ViewBatch& b, float ssim_fac,
-                              bool sums_cleared, const DepthPrior& dp, const ExposureReg& ex, const LossWeight& lw,
-                              const StepImages& im, const Background& bg = Background{},
-                              const AlphaTarget& at = AlphaTarget{}) {
+                              bool sums_cleared, const StepImages& im) {
+    const WeightedTarget &dp = b.opt.dp, &at = b.opt.at;
+    const ExposureReg& ex = b.opt.ex;
+    const LossWeight& lw = b.opt.lw;
+    const Background& bg = b.opt.bg;
+    // dp.map != NULL: the step also renders the depth map of the same lists and takes the prior's loss, which sends v_D
+    // and v_alpha back
     // bg.colors != NULL: the loss sees the render composited over the views' backgrounds (st3r_composite_fwd, into scratch
-    // of its own, before the exposure: scene first, then camera); at.target != NULL: the alpha term.  Either one sends a
+    // of its own, before the exposure: scene first, then camera); at.map != NULL: the alpha term.  Either one sends a
     // v_alpha back (st3r_alpha_grad, behind the depth prior, onto whose v_alpha it accumulates)
     // ex.exposure != NULL: the loss compares y = E x with the ground truth (the stand-alone kernels of gs_exposure.hip, in
     // the order of the unfused chain); im.v_rgb leaves as d loss / d x, ex.v_exposure as d loss / d E of these views
@@ -327,7 +323,7 @@ static int forward_and_losses(st3r_ctx* ctx, hipStream_t s, const RasterOut& ro,
     const bool eio = true;   // the fused path's offsets table carries the total as its last entry
     st3r_prof_begin(ctx, s, STG_BLEND_FWD);
     int rc = st3r_blend_fwd_impl(ctx, s, ro, im.rgb, im.alpha, im.last, true, eio);
-    if (!rc && dp.prior) rc = st3r_blend_depth_fwd_impl(ctx, s, ro, im.last, im.depth, eio);
+    if (!rc && dp.map) rc = st3r_blend_depth_fwd_impl(ctx, s, ro, im.last, im.depth, eio);
     st3r_prof_end(ctx, s, STG_BLEND_FWD);
     if (rc) return rc;
     st3r_prof_begin(ctx, s, STG_LOSS);
@@ -342,12 +338,12 @@ static int forward_and_losses(st3r_ctx* ctx, hipStream_t s, const RasterOut& ro,
                             b.sums, im.v_rgb, sums_cleared, lw);
     if (!rc && ex.exposure)
         rc = st3r_exposure_bwd_impl(ctx, s, ro.C, ro.H, ro.W, x, ex.exposure, im.v_rgb, im.v_rgb, ex.v_exposure);
-    if (!rc && dp.prior)
-        rc = st3r_depth_prior_loss_impl(ctx, s, ro.C, ro.H, ro.W, im.depth, im.alpha, dp.prior, dp.weight, dp.norm, 1, dp.fac,
-                                        b.dp_sums, 1, im.v_depth, im.v_alpha);
-    if (!rc && (bg.colors || at.target))   // im.v_rgb is d loss / d composite here, and d loss / d render as it stands
-        rc = st3r_alpha_grad_impl(ctx, s, ro.C, ro.H, ro.W, im.alpha, bg.colors, bg.colors ? im.v_rgb : nullptr, at.target,
-                                  at.weight, at.norm, 1, at.fac, dp.prior ? im.v_alpha : nullptr, b.at_sums, 1, im.v_alpha,
+    if (!rc && dp.map)
+        rc = st3r_depth_prior_loss_impl(ctx, s, ro.C, ro.H, ro.W, im.depth, im.alpha, dp.map, dp.weight, dp.norm, 1, dp.fac,
+                                        b.opt.dp_sums, 1, im.v_depth, im.v_alpha);
+    if (!rc && (bg.colors || at.map))   // im.v_rgb is d loss / d composite here, and d loss / d render as it stands
+        rc = st3r_alpha_grad_impl(ctx, s, ro.C, ro.H, ro.W, im.alpha, bg.colors, bg.colors ? im.v_rgb : nullptr, at.map,
+                                  at.weight, at.norm, 1, at.fac, dp.map ? im.v_alpha : nullptr, b.opt.at_sums, 1, im.v_alpha,
                                   nullptr);
     st3r_prof_end(ctx, s, STG_LOSS);
     return rc;
@@ -415,44 +411,30 @@ static int pose_backward(st3r_ctx* ctx, hipStream_t s, const GsParams& g, const 
 }
 
 // The views of b in one training call: rasterize -> loss -> backward; the parameter gradients are written
-// (accumulate = false) or added (later view chunks of the same call).  b.dp_sums != NULL: a depth prior may be registered
-// for these views (st3r_ctx_set_depth_prior).  b.v_viewmats != NULL (st3r_gs_train_step_poses): the gradient of these
-// views' world-to-camera matrices is written as well.
+// (accumulate = false) or added (later view chunks of the same call).  b.opt: what is registered for these views.
+// b.v_viewmats != NULL (st3r_gs_train_step_poses): the gradient of these views' world-to-camera matrices is written as well.
 static int train_views(st3r_ctx* ctx, hipStream_t s, const GsParams& g, const ViewBatch& b, const LossFacs& f,
                        double* reg_sums, bool allow_async, bool accumulate, float* grads, RasterOut* ro_out) {
     const GsViews& v = b.v;
-    DepthPrior dp{};
-    int rc = b.dp_sums ? st3r_depth_prior_for(ctx, s, b.gt, v.C, v.H, v.W, &dp) : ST3R_OK;
-    if (rc) return rc;
-    ExposureReg ex{};
-    if (b.exposure) st3r_exposure_for(ctx, b.gt, v.C, v.H, v.W, &ex);
-    LossWeight lw{};
-    if (b.weighted) rc = st3r_loss_weight_for(ctx, s, b.gt, v.C, v.H, v.W, &lw);
-    if (rc) return rc;
-    Background bg{};
-    if (b.background) st3r_background_for(ctx, b.gt, v.C, v.H, v.W, &bg);
-    AlphaTarget at{};
-    if (b.at_sums) rc = st3r_alpha_target_for(ctx, s, b.gt, v.C, v.H, v.W, &at);
-    if (rc) return rc;
     // The one decision: with a depth prior the projection backward reads the per-pair array v_pairs (colour + depth
     // gradients, added), without one it sums the colour backward's slots itself (backgrounds and alpha targets hand the
     // colour backward a v_alpha as the depth prior does; its slots then carry the alpha path, and need_pairs stays false).
-    const bool need_pairs = dp.prior != nullptr;
+    const bool need_pairs = b.opt.dp.map != nullptr;
     RasterOut& ro = *ro_out;
-    rc = rasterize_front(ctx, s, g, v, reg_sums, 1, nullptr, allow_async, &ro, b.sums);
+    int rc = rasterize_front(ctx, s, g, v, reg_sums, 1, nullptr, allow_async, &ro, b.sums);
     if (rc) return rc;
     StepImages im;
-    rc = step_images(ctx, ro, need_pairs, ex.exposure != nullptr, bg.colors != nullptr, bg.colors || at.target, &im);
+    rc = step_images(ctx, ro, b.opt, &im);
     if (rc) return rc;
     // an intrinsics gradient registered for these views (st3r_ctx_set_intrinsics_grad): it needs the per-pair array as
     // the pose gradient does
-    float* const v_Ks = st3r_intrinsics_grad_for(ctx, b.gt, v.C, v.H, v.W);
+    float* const v_Ks = b.opt.v_Ks;
     float* v_pairs = nullptr;   // per-pair gradients [N*C, 12]: the projection backward's input and / or the pose backward's
     if (need_pairs || b.v_viewmats || v_Ks) {
         ARENA_GET(SLOT_VSPLATS, float, ro.n_pairs * ST3R_SPLAT_STRIDE, vp);
         v_pairs = vp;
     }
-    rc = forward_and_losses(ctx, s, ro, b, f.ssim, true, dp, ex, lw, im, bg, at);
+    rc = forward_and_losses(ctx, s, ro, b, f.ssim, true, im);
     if (rc) return rc;
     st3r_vtile_ref slots{};
     rc = blend_backward(ctx, s, ro, im, need_pairs, &slots, v_pairs);
@@ -512,6 +494,44 @@ static int train_chunks(st3r_ctx* ctx, hipStream_t s, const GsParams& g, const V
     }
 }
 
+// The registered weighted target r (ctx->dp or ctx->at, with its two arena slots) that belongs to the C views at `gt`:
+// out->map = NULL if there is none (no registration that applies -- view_reg_first -- or a factor of 0).
+static int weighted_target_for(st3r_ctx* ctx, hipStream_t s, TargetReg* r, int part_slot, int norm_slot, const float* gt,
+                               int C, int H, int W, WeightedTarget* out) {
+    *out = WeightedTarget{};
+    const int64_t c0 = view_reg_first(r->reg, gt, C, H, W), HW = (int64_t)H * W;
+    if (c0 < 0 || r->fac == 0.f) return ST3R_OK;
+    const double* n_c;
+    int rc = st3r_registered_weight_norms(ctx, s, r->reg, r->weight, 1, false, part_slot, norm_slot, &r->norm_valid, &n_c);
+    if (rc) return rc;
+    *out = WeightedTarget{r->map + c0 * HW, r->weight + c0 * HW, n_c + c0, r->fac};
+    return ST3R_OK;
+}
+
+// Everything registered for the C views at `gt`, each option looked up once, in this order: it is the order of the
+// once-per-registration norm launches (st3r_registered_weight_norms).  The view chunks of the call slice the result.
+static int resolve_options(st3r_ctx* ctx, hipStream_t s, const float* gt, int C, int H, int W, StepOptions* o) {
+    *o = StepOptions{};
+    int rc = weighted_target_for(ctx, s, &ctx->dp, SLOT_DPRIOR_PART, SLOT_DPRIOR_NORM, gt, C, H, W, &o->dp);
+    if (rc) return rc;
+    st3r_exposure_for(ctx, gt, C, H, W, &o->ex);
+    o->v_Ks = st3r_intrinsics_grad_for(ctx, gt, C, H, W);
+    rc = st3r_loss_weight_for(ctx, s, gt, C, H, W, &o->lw);
+    if (rc) return rc;
+    st3r_background_for(ctx, gt, C, H, W, &o->bg);
+    rc = weighted_target_for(ctx, s, &ctx->at, SLOT_ATARGET_PART, SLOT_ATARGET_NORM, gt, C, H, W, &o->at);
+    if (rc) return rc;
+    if (o->dp.map) {
+        ARENA_GET(SLOT_DPRIOR_SUMS, double, (size_t)C, sums);
+        o->dp_sums = sums;
+    }
+    if (o->at.map) {
+        ARENA_GET(SLOT_ATARGET_SUMS, double, (size_t)C, sums);
+        o->at_sums = sums;
+    }
+    return ST3R_OK;
+}
+
 int st3r_train_fwd_bwd_impl(st3r_ctx* ctx, hipStream_t s, const GsParams& g, const GsViews& v, const float* gt_images,
                             float ssim_fac, float opac_fac, float scale_fac, float* grads, float* loss_out,
                             int64_t* stats_host, float* v_viewmats) {
@@ -523,81 +543,32 @@ int st3r_train_fwd_bwd_impl(st3r_ctx* ctx, hipStream_t s, const GsParams& g, con
     ARENA_GET(SLOT_SMALL, double, 2 * (size_t)C + 12, small);
     double* sums = small;              // [C,2]
     double* reg_sums = small + 2 * C;  // [4]: sum sigmoid(o), sum exp(s), visible pairs, reference intersections
-    // a depth prior registered for these views (st3r_ctx_set_depth_prior): its per-view sums, and whether it applies at all
-    double* dp_sums = nullptr;
-    DepthPrior dp;
-    int rc = st3r_depth_prior_for(ctx, s, gt_images, C, v.H, v.W, &dp);
+    StepOptions opt;
+    int rc = resolve_options(ctx, s, gt_images, C, v.H, v.W, &opt);
     if (rc) return rc;
-    if (dp.prior) {
-        if (ctx->comm) {
-            st3r_set_error("a depth prior is registered and a communicator is attached -- the depth term is not "
-                           "supported in view-sharded training (clear it with st3r_ctx_set_depth_prior(ctx, NULL, ...))");
-            return ST3R_ERR_INVALID;
-        }
-        ARENA_GET(SLOT_DPRIOR_SUMS, double, (size_t)C, ds);
-        dp_sums = ds;
-    }
-    // exposures registered for these views (st3r_ctx_set_exposure): the depth prior's rule under a communicator
-    ExposureReg ex;
-    st3r_exposure_for(ctx, gt_images, C, v.H, v.W, &ex);
-    if (ex.exposure && ctx->comm) {
-        st3r_set_error("exposures are registered and a communicator is attached -- per-view exposures are not supported "
-                       "in view-sharded training (clear them with st3r_ctx_set_exposure(ctx, NULL, ...))");
-        return ST3R_ERR_INVALID;
-    }
-    // an intrinsics gradient registered for these views (st3r_ctx_set_intrinsics_grad): the same rule
-    if (ctx->comm && st3r_intrinsics_grad_for(ctx, gt_images, C, v.H, v.W)) {
-        st3r_set_error("an intrinsics gradient is registered and a communicator is attached -- intrinsics refinement is "
-                       "not supported in view-sharded training (clear it with st3r_ctx_set_intrinsics_grad(ctx, NULL, ...))");
-        return ST3R_ERR_INVALID;
-    }
-    // per-pixel loss weights registered for these views (st3r_ctx_set_loss_weight): the same rule
-    LossWeight lw;
-    rc = st3r_loss_weight_for(ctx, s, gt_images, C, v.H, v.W, &lw);
-    if (rc) return rc;
-    if (lw.weight && ctx->comm) {
-        st3r_set_error("loss weights are registered and a communicator is attached -- per-pixel loss weights are not "
-                       "supported in view-sharded training (clear them with st3r_ctx_set_loss_weight(ctx, NULL, ...))");
-        return ST3R_ERR_INVALID;
-    }
-    // backgrounds registered for these views (st3r_ctx_set_background): the same rule
-    Background bg;
-    st3r_background_for(ctx, gt_images, C, v.H, v.W, &bg);
-    if (bg.colors && ctx->comm) {
-        st3r_set_error("backgrounds are registered and a communicator is attached -- backgrounds are not supported in "
-                       "view-sharded training (clear them with st3r_ctx_set_background(ctx, NULL, ...))");
-        return ST3R_ERR_INVALID;
-    }
-    // alpha targets registered for these views (st3r_ctx_set_alpha_target): their per-view sums, and the same rule
-    double* at_sums = nullptr;
-    AlphaTarget at;
-    rc = st3r_alpha_target_for(ctx, s, gt_images, C, v.H, v.W, &at);
-    if (rc) return rc;
-    if (at.target) {
-        if (ctx->comm) {
-            st3r_set_error("alpha targets are registered and a communicator is attached -- alpha supervision is not "
-                           "supported in view-sharded training (clear them with st3r_ctx_set_alpha_target(ctx, NULL, ...))");
-            return ST3R_ERR_INVALID;
-        }
-        ARENA_GET(SLOT_ATARGET_SUMS, double, (size_t)C, as);
-        at_sums = as;
-    }
-    // an SH degree other than the default (st3r_ctx_set_sh_degree): the same rule
-    if (ctx->comm && !(ctx->sh_degree == 1 && ctx->sh_active == 1)) {
-        st3r_set_error("the SH degree is set and a communicator is attached -- SH degrees other than 1 are not supported "
-                       "in view-sharded training (restore it with st3r_ctx_set_sh_degree(ctx, 1, 1, NULL))");
-        return ST3R_ERR_INVALID;
+    const bool activated = ctx->activation != 0;   // activated parameters (st3r_ctx_set_activation)
+    if (ctx->comm) {   // view-sharded training takes none of the options: refuse before anything of the caller's is written
+        const struct { bool applies; const char *what, *clear; } refused[] = {
+            {opt.dp.map != nullptr, "a depth prior is registered", "st3r_ctx_set_depth_prior(ctx, NULL, ...)"},
+            {opt.ex.exposure != nullptr, "exposures are registered", "st3r_ctx_set_exposure(ctx, NULL, ...)"},
+            {opt.v_Ks != nullptr, "an intrinsics gradient is registered", "st3r_ctx_set_intrinsics_grad(ctx, NULL, ...)"},
+            {opt.lw.weight != nullptr, "loss weights are registered", "st3r_ctx_set_loss_weight(ctx, NULL, ...)"},
+            {opt.bg.colors != nullptr, "backgrounds are registered", "st3r_ctx_set_background(ctx, NULL, ...)"},
+            {opt.at.map != nullptr, "alpha targets are registered", "st3r_ctx_set_alpha_target(ctx, NULL, ...)"},
+            {!(ctx->sh_degree == 1 && ctx->sh_active == 1), "an SH degree other than 1 is set",
+             "st3r_ctx_set_sh_degree(ctx, 1, 1, NULL)"},
+            {activated, "the activation is on", "st3r_ctx_set_activation(ctx, 0)"},
+        };
+        for (const auto& r : refused)
+            if (r.applies) {
+                st3r_set_error("%s and a communicator is attached -- view-sharded training does not support it (clear it "
+                               "with %s)", r.what, r.clear);
+                return ST3R_ERR_INVALID;
+            }
     }
     GsParams gsh = g;
     rc = st3r_sh_setting(ctx, &gsh, true);
     if (rc) return rc;
-    // activated parameters (st3r_ctx_set_activation): the same rule
-    const bool activated = ctx->activation != 0;
-    if (activated && ctx->comm) {
-        st3r_set_error("the activation is on and a communicator is attached -- activated scales and opacities are not "
-                       "supported in view-sharded training (clear it with st3r_ctx_set_activation(ctx, 0))");
-        return ST3R_ERR_INVALID;
-    }
     st3r_prof_next_step(ctx);
     rc = st3r_count_settle(ctx);
     if (rc) return rc;
@@ -616,8 +587,7 @@ int st3r_train_fwd_bwd_impl(st3r_ctx* ctx, hipStream_t s, const GsParams& g, con
     if ((ctx->debug_flags & 32) && chunks < 2) chunks = 2;
     if (chunks > C) chunks = C;
     int64_t stats[3];
-    rc = train_chunks(ctx, s, ga, ViewBatch{v, gt_images, sums, dp_sums, v_viewmats, ex.exposure != nullptr, lw.weight != nullptr,
-                                            bg.colors != nullptr, at_sums},
+    rc = train_chunks(ctx, s, ga, ViewBatch{v, gt_images, sums, v_viewmats, opt},
                       activated ? LossFacs{ssim_fac, 0.f, 0.f} : LossFacs{ssim_fac, opac_fac, scale_fac},
                       reg_sums, reg_sums + 4, stats_host != nullptr, grads, &chunks, stats);
     if (rc) return rc;
@@ -633,7 +603,7 @@ int st3r_train_fwd_bwd_impl(st3r_ctx* ctx, hipStream_t s, const GsParams& g, con
         if (rc) return rc;
     }
     rc = finalize_loss(s, C, v.H, v.W, sums, activated ? act_sums : reg_sums, ssim_fac, (double)C, (double)opac_fac / N,
-                       (double)scale_fac / (3.0 * N), loss_out, dp_sums, dp, lw, at_sums, at);
+                       (double)scale_fac / (3.0 * N), loss_out, opt);
     if (rc) return rc;
     if (stats_host) {
         stats_host[0] = stats[0]; stats_host[1] = stats[1]; stats_host[2] = st3r_ctx_arena_bytes(ctx);
@@ -664,7 +634,7 @@ ST3R_EXPORT int st3r_gs_raster_train(st3r_ctx* ctx, void* stream, int N, int C, 
     hipStream_t s = (hipStream_t)stream;
     ARENA_GET(SLOT_SMALL, double, 2 * (size_t)C + 8, sums);
     double* reg_sums = sums + 2 * C;
-    const ViewBatch b{GsViews{C, width, height}, gt_images, sums, nullptr, nullptr, false, false, false, nullptr};   // (no camera is looked at)
+    const ViewBatch b{GsViews{C, width, height}, gt_images, sums, nullptr, StepOptions{}};   // (no camera is looked at, no option)
     HIP_TRY(hipMemsetAsync(reg_sums, 0, sizeof(double) * 4, s));  // stays zero: the regularisers belong to the owners
     st3r_prof_next_step(ctx);
     RasterOut ro;
@@ -674,16 +644,15 @@ ST3R_EXPORT int st3r_gs_raster_train(st3r_ctx* ctx, void* stream, int N, int C, 
     if (rc == ST3R_SPLIT_VIEWS) rc = ST3R_ERR_INVALID;
     if (rc) return rc;
     StepImages im;
-    rc = step_images(ctx, ro, false, false, false, false, &im);
+    rc = step_images(ctx, ro, b.opt, &im);
     if (rc) return rc;
-    rc = forward_and_losses(ctx, s, ro, b, ssim_fac, false, DepthPrior{}, ExposureReg{}, LossWeight{}, im);
+    rc = forward_and_losses(ctx, s, ro, b, ssim_fac, false, im);
     if (rc) return rc;
     st3r_prof_begin(ctx, s, STG_BLEND_BWD);
     rc = st3r_blend_bwd_impl(ctx, s, ro, im.alpha, im.last, im.v_rgb, nullptr, v_records, true, nullptr);
     st3r_prof_end(ctx, s, STG_BLEND_BWD);
     if (rc) return rc;
-    rc = finalize_loss(s, C, height, width, sums, reg_sums, ssim_fac, 0.0, 0.0, 0.0, loss_out, nullptr, DepthPrior{},
-                       LossWeight{});
+    rc = finalize_loss(s, C, height, width, sums, reg_sums, ssim_fac, 0.0, 0.0, 0.0, loss_out, b.opt);
     if (rc) return rc;
     if (stats_host) {
         stats_host[0] = -1; stats_host[1] = ro.n_records; stats_host[2] = st3r_ctx_arena_bytes(ctx); stats_host[3] = -1;

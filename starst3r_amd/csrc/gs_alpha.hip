@@ -192,20 +192,6 @@ void st3r_background_for(st3r_ctx* ctx, const float* gt, int C, int H, int W, Ba
     *out = c0 < 0 ? Background{} : Background{ctx->bg_colors + 3 * c0};
 }
 
-// The registered alpha targets that belong to the C views at `gt`: out->target = NULL if there are none (no registration
-// that applies, or alpha_fac == 0) -- the rules of st3r_depth_prior_for.
-int st3r_alpha_target_for(st3r_ctx* ctx, hipStream_t s, const float* gt, int C, int H, int W, AlphaTarget* out) {
-    *out = AlphaTarget{};
-    const int64_t c0 = view_reg_first(ctx->at, gt, C, H, W), HW = (int64_t)H * W;
-    if (c0 < 0 || ctx->at_fac == 0.f) return ST3R_OK;
-    const double* n_c;
-    int rc = st3r_registered_weight_norms(ctx, s, ctx->at, ctx->at_weight, 1, false, SLOT_ATARGET_PART, SLOT_ATARGET_NORM,
-                                          &ctx->at_norm_valid, &n_c);
-    if (rc) return rc;
-    *out = AlphaTarget{ctx->at_target + c0 * HW, ctx->at_weight + c0 * HW, n_c + c0, ctx->at_fac};
-    return ST3R_OK;
-}
-
 ST3R_EXPORT int st3r_ctx_set_background(st3r_ctx* ctx, const float* gt, const float* backgrounds, int C, int height,
                                         int width) {
     ARG_CHECK(ctx);
@@ -219,13 +205,7 @@ ST3R_EXPORT int st3r_ctx_set_background(st3r_ctx* ctx, const float* gt, const fl
 ST3R_EXPORT int st3r_ctx_set_alpha_target(st3r_ctx* ctx, const float* gt, const float* target, const float* weight, int C,
                                           int height, int width, float alpha_fac) {
     ARG_CHECK(ctx);
-    ctx->at_norm_valid = 0;
-    const bool on = gt && target && weight;
-    ARG_CHECK(!on || alpha_fac - alpha_fac == 0.f);   // finite
-    int rc = view_reg_set(&ctx->at, on, gt, C, height, width);
-    if (rc) return rc;
-    ctx->at_target = on ? target : nullptr; ctx->at_weight = on ? weight : nullptr; ctx->at_fac = on ? alpha_fac : 0.f;
-    return ST3R_OK;
+    return target_reg_set(&ctx->at, gt, target, weight, C, height, width, alpha_fac, alpha_fac - alpha_fac == 0.f);   // finite
 }
 
 ST3R_EXPORT int st3r_composite_fwd(st3r_ctx* ctx, void* stream, int C, int height, int width, const float* rgb,

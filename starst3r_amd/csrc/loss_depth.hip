@@ -109,30 +109,10 @@ int st3r_depth_prior_loss_impl(st3r_ctx* ctx, hipStream_t s, int C, int H, int W
     return stream_finish<1>(s, C, blocks, part, sums, sums_stride, 0);
 }
 
-// The registered prior that belongs to the C views at `gt` (fused_step.hip): out->prior = NULL if there is none (no
-// registration that applies -- view_reg_first -- or depth_fac == 0).
-int st3r_depth_prior_for(st3r_ctx* ctx, hipStream_t s, const float* gt, int C, int H, int W, DepthPrior* out) {
-    *out = DepthPrior{};
-    const int64_t c0 = view_reg_first(ctx->dp, gt, C, H, W), HW = (int64_t)H * W;
-    if (c0 < 0 || ctx->dp_fac == 0.f) return ST3R_OK;
-    const double* n_c;
-    int rc = st3r_registered_weight_norms(ctx, s, ctx->dp, ctx->dp_weight, 1, false, SLOT_DPRIOR_PART, SLOT_DPRIOR_NORM,
-                                          &ctx->dp_norm_valid, &n_c);
-    if (rc) return rc;
-    *out = DepthPrior{ctx->dp_depth + c0 * HW, ctx->dp_weight + c0 * HW, n_c + c0, ctx->dp_fac};
-    return ST3R_OK;
-}
-
 ST3R_EXPORT int st3r_ctx_set_depth_prior(st3r_ctx* ctx, const float* gt, const float* depth, const float* weight, int C,
                                          int height, int width, float depth_fac) {
     ARG_CHECK(ctx);
-    ctx->dp_norm_valid = 0;
-    const bool on = gt && depth && weight;
-    ARG_CHECK(!on || depth_fac == depth_fac);
-    int rc = view_reg_set(&ctx->dp, on, gt, C, height, width);
-    if (rc) return rc;
-    ctx->dp_depth = on ? depth : nullptr; ctx->dp_weight = on ? weight : nullptr; ctx->dp_fac = on ? depth_fac : 0.f;
-    return ST3R_OK;
+    return target_reg_set(&ctx->dp, gt, depth, weight, C, height, width, depth_fac, depth_fac == depth_fac);   // no NaN
 }
 
 ST3R_EXPORT int st3r_loss_depth_prior(st3r_ctx* ctx, void* stream, int C, int height, int width, const float* depth,

@@ -57,8 +57,9 @@ static inline RasterOut stage_lists(int C, int W, int H, int tile_w, int tile_h,
                      n_isects, -1};
 }
 
-// the registered depth prior of a set of views (loss_depth.hip); prior == NULL: none applies
-struct DepthPrior { const float* prior; const float* weight; const double* norm; float fac; };
+// a registered weighted per-pixel target of a set of views -- the depth prior (loss_depth.hip), the alpha targets
+// (gs_alpha.hip): map, weight [C,H,W], norm [C] = n_c, fac of its loss term; map == NULL: none applies
+struct WeightedTarget { const float* map; const float* weight; const double* norm; float fac; };
 
 // the registered exposures of a set of views (gs_exposure.hip) and where their gradient goes; exposure == NULL: none applies
 struct ExposureReg { const float* exposure; float* v_exposure; };
@@ -71,8 +72,30 @@ struct LossWeight { const float* weight = nullptr; const double* norm = nullptr;
 // the registered backgrounds [C,3] of a set of views (gs_alpha.hip); colors == NULL: none apply
 struct Background { const float* colors; };
 
-// the registered alpha targets of a set of views (gs_alpha.hip): target, weight [C,H,W], norm [C]; target == NULL: none apply
-struct AlphaTarget { const float* target; const float* weight; const double* norm; float fac; };
+// What a training call's views have registered (st3r_ctx_set_*), resolved once per call (fused_step.hip:
+// resolve_options); default-constructed: nothing applies.  dp_sums, at_sums [C]: the per-view sums sum_p w |ED - Z| and
+// sum_p w |a - M| of the step; v_Ks [C,4]: the rows of the registered intrinsics gradient (gs_intrinsics.hip).
+struct StepOptions {
+    WeightedTarget dp{}; double* dp_sums = nullptr;   // depth prior
+    ExposureReg ex{};
+    LossWeight lw{};
+    Background bg{};
+    WeightedTarget at{}; double* at_sums = nullptr;   // alpha targets
+    float* v_Ks = nullptr;
+    // the options of the views from c0 on (HW pixels each): every per-view pointer moves by c0 whole views -- what
+    // view_reg_first yields for those views' ground-truth pointer
+    StepOptions slice(int c0, int64_t HW) const {
+        StepOptions o = *this;
+        const auto move = [c0](auto*& p, int64_t per_view) { if (p) p += c0 * per_view; };
+        move(o.dp.map, HW); move(o.dp.weight, HW); move(o.dp.norm, 1); move(o.dp_sums, 1);
+        move(o.ex.exposure, 12); move(o.ex.v_exposure, 12);
+        move(o.lw.weight, HW); move(o.lw.norm, o.lw.norm_stride);
+        move(o.bg.colors, 3);
+        move(o.at.map, HW); move(o.at.weight, HW); move(o.at.norm, 1); move(o.at_sums, 1);
+        move(o.v_Ks, 4);
+        return o;
+    }
+};
 
 // ---- api.hip, fused_step.hip, comm.hip ----
 // The 16 device words next to the fused steps: [0] record count of an asynchronous step (k_adam compares it with the
@@ -147,7 +170,6 @@ int st3r_weight_norms(st3r_ctx* ctx, hipStream_t s, int C, int H, int W, const f
                       int at_least_one, bool interior, int slot);
 int st3r_registered_weight_norms(st3r_ctx* ctx, hipStream_t s, const ViewReg& reg, const float* weight, int at_least_one,
                                  bool interior, int part_slot, int norm_slot, int* valid, const double** norms);
-int st3r_depth_prior_for(st3r_ctx* ctx, hipStream_t s, const float* gt, int C, int H, int W, DepthPrior* out);
 int st3r_depth_prior_loss_impl(st3r_ctx* ctx, hipStream_t s, int C, int H, int W, const float* depth, const float* alpha,
                                const float* prior, const float* weight, const double* norm, int norm_stride,
                                float depth_fac, double* sums, int sums_stride, float* v_depth, float* v_alpha);
@@ -160,7 +182,6 @@ int st3r_exposure_bwd_impl(st3r_ctx* ctx, hipStream_t s, int C, int H, int W, co
 
 // ---- gs_alpha.hip ----
 void st3r_background_for(st3r_ctx* ctx, const float* gt, int C, int H, int W, Background* out);
-int st3r_alpha_target_for(st3r_ctx* ctx, hipStream_t s, const float* gt, int C, int H, int W, AlphaTarget* out);
 int st3r_composite_fwd_impl(hipStream_t s, int C, int H, int W, const float* rgb, const float* alpha,
                             const float* backgrounds, float* out);
 int st3r_alpha_grad_impl(st3r_ctx* ctx, hipStream_t s, int C, int H, int W, const float* alpha, const float* backgrounds,

@@ -1,6 +1,6 @@
-"""'Registered for these views': the one look-up (view_reg_first, csrc/common.h) behind the three registrations of a
-context -- ground-truth moments, depth prior, exposures -- at its edges, once per registration, and run_3dgs_optim's
-clean-up when a registration itself fails.
+"""'Registered for these views': the one look-up (view_reg_first, csrc/common.h) behind the seven registrations of a
+context -- ground-truth moments, depth prior, exposures, intrinsics gradient, loss weights, backgrounds, alpha targets --
+at its edges, once per registration, and run_3dgs_optim's clean-up when a registration itself fails.
 
 A registration applies to a call on the registered images or on a whole-view offset into them (view chunks), and then
 gives the bits of a fresh registration of exactly those views; it does not apply to the same pixels at another address,
@@ -38,9 +38,20 @@ class _Case:
             Z, wt, _ = _synthetic_prior(self.ctx, self.P, self.vm, self.K, W, H)
             assert all(float(wt[c].sum()) > 0 for c in range(V))
             self.payload = (Z, wt)
-        else:
+        elif kind == "exposure":
             E = (torch.eye(3, 4) + 0.1 * torch.randn((V, 3, 4), generator=gen)).cuda()
             self.payload = (E, torch.zeros((V, 3, 4), device="cuda:0"))
+        elif kind == "intrinsics_grad":
+            self.payload = (torch.zeros((V, 4), device="cuda:0"),)
+        elif kind == "background":
+            self.payload = (torch.rand((V, 3), generator=gen).cuda(),)
+        else:   # loss_weight: the weights; alpha_target: the targets and their weights -- with holes
+            maps = [torch.rand((V, H, W), generator=gen) for _ in range(1 if kind == "loss_weight" else 2)]
+            maps[-1][torch.rand((V, H, W), generator=gen) < 0.3] = 0.0
+            assert all(float(maps[-1][c].sum()) > 0 and float(maps[-1][c, 5:-5, 5:-5].sum()) > 0 for c in range(V))
+            self.payload = tuple(m.cuda() for m in maps)
+        # the buffer a call writes besides grads (its rows keep -1 where the call does not write): v_exposure, v_Ks
+        self.written = {"exposure": 1, "intrinsics_grad": 0}.get(kind)
 
     def set(self, k=0, n=V, gt=None):
         gt = self.gt[k:k + n] if gt is None else gt
@@ -49,13 +60,25 @@ class _Case:
             self.ops.set_gt_moments(self.ctx, gt, part[0].reshape(*gt.shape, 2))
         elif self.kind == "depth_prior":
             self.ops.set_depth_prior(self.ctx, gt, part[0].reshape(gt.shape[:3]), part[1].reshape(gt.shape[:3]), 0.5)
-        else:
+        elif self.kind == "exposure":
             self.ops.set_exposure(self.ctx, gt, *part)
+        elif self.kind == "intrinsics_grad":
+            self.ops.set_intrinsics_grad(self.ctx, gt, part[0])
+        elif self.kind == "loss_weight":
+            self.ops.set_loss_weight(self.ctx, gt, part[0].reshape(gt.shape[:3]))
+        elif self.kind == "background":
+            self.ops.set_background(self.ctx, gt, part[0])
+        else:
+            self.ops.set_alpha_target(self.ctx, gt, part[0].reshape(gt.shape[:3]), part[1].reshape(gt.shape[:3]), 0.5)
 
     def clear(self):
         self.ops.set_gt_moments(self.ctx, None, None)
         self.ops.set_depth_prior(self.ctx, None, None, None)
         self.ops.set_exposure(self.ctx, None, None, None)
+        self.ops.set_intrinsics_grad(self.ctx, None, None)
+        self.ops.set_loss_weight(self.ctx, None, None)
+        self.ops.set_background(self.ctx, None, None)
+        self.ops.set_alpha_target(self.ctx, None, None, None)
 
     def call(self, gt, k=0):
         """the gradient of a call on the views [k, k + gt.shape[0]) with the images gt (any size with H * W pixels)"""
@@ -65,11 +88,11 @@ class _Case:
             out = [v]
         else:
             grads, loss = torch.empty(23 * N, device="cuda:0"), torch.zeros(1, device="cuda:0")
-            if self.kind == "exposure":
-                self.payload[1].fill_(-1.0)   # v_exposure: rows a call does not write keep this
+            if self.written is not None:
+                self.payload[self.written].fill_(-1.0)   # v_exposure, v_Ks: rows a call does not write keep this
             self.ops.train_fwd_bwd(self.ctx, self.P, self.vm[k:k + n], self.K[k:k + n], self.campos[k:k + n], gt, w, h, 0.2,
                                    0.01, 0.01, grads, loss)
-            out = [grads] + ([self.payload[1].clone()] if self.kind == "exposure" else [])
+            out = [grads] + ([self.payload[self.written].clone()] if self.written is not None else [])
         torch.cuda.synchronize()
         return out
 
@@ -78,7 +101,8 @@ def _same(a, b):
     return all(_same_bits(x, y) for x, y in zip(a, b))
 
 
-@pytest.mark.parametrize("kind", ["moments", "depth_prior", "exposure"])
+@pytest.mark.parametrize("kind", ["moments", "depth_prior", "exposure", "intrinsics_grad", "loss_weight", "background",
+                                  "alpha_target"])
 def test_registration_applies_to_whole_view_slices_and_to_nothing_else(kind):
     c = _Case(kind)
     try:
